@@ -2,7 +2,18 @@
 """Benchmark: training steps of the "magic" metric-VAE (``TangoEncoder.partial_fit``,
 reference ``11a/vae.py:385-411``) on MI355X through libmvae's HIP kernels.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and no more: set up, W warm-up steps, K timed
+steps, the result line. ``--full`` adds every other measurement and check of this file: the
+region pass and the rooflines (with the rocprofv3 counter passes), the CPU baseline and its
+parity check, the PCIe-inclusive and input-pipeline legs, the held-out overlap-MSE and the
+configs block (C3 / C5 / C5CONV; C4 / C5 with N ranks). The ``--no-*`` switches, ``--pmc``,
+``--region-steps`` and ``--mark-dominant`` shape a ``--full`` run.
+
+``--dump-outputs DIR`` writes what the last timed step left for its caller as ``DIR/<name>.npy``
+(see ``dump_outputs``). Parameters, batches and the eps stream are seeded, so two runs with the
+same arguments start from identical inputs.
 
 ``--gpus N`` with N > 1 and no torchrun environment starts N local ranks itself
 (``torch.distributed.run``, one process per GPU, RCCL); under torchrun it is one of them.
@@ -12,8 +23,8 @@ resident in HBM: de-interleave, eps sampling, 3 encoder passes, decoder, five-lo
 both gradients, (N > 1: RCCL all-reduces), both Adam updates. Weak scaling: the per-GPU
 batch is fixed; ``value`` = pairs processed by ALL ranks / max-over-ranks wall time.
 
-Rank 0 prints ONE JSON line; per-region HIP-event timings go to stderr. Besides the
-contract's fields the line carries:
+Rank 0 prints ONE JSON line; with ``--full`` per-region HIP-event timings go to stderr and,
+besides the contract's fields, the line carries (null in a plain run):
   roofline       the dominant GEMM: algorithmic FLOPs (2*M*N*K once) / its
                  mean HIP-event duration in the timed loop, against the dense MFMA peak of
                  the arithmetic it runs on; f32x (fp32-accurate bf16 plane split) adds
@@ -50,6 +61,8 @@ METRIC = "shape-pairs/sec/GPU (train step) + overlap-MSE, 100×100 pairs, 1/2/4/
 F32_MFMA_PEAK_TFLOPS = 157.3     # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32 (exact fp32)
 BF16_MFMA_PEAK_TFLOPS = 2500.0   # dense
 HBM_PEAK_GBS = 8000.0
+DUMP_MAX_ELEMS = 4 << 20        # --dump-outputs: values written per buffer (16 MB of float32)
+DUMP_SEED = 20250
 PMC_REGIONS_BW = ("deinterleave", "deint_fwd0", "latent_bwd", "adam")
 # the layer-0 pair and the decoder-output trio: HBM traffic and the MFMA-busy fraction per region
 PMC_REGIONS_MFMA = ("enc_fwd_0", "enc_bwd_w_0", "dec_fwd_out_bce", "dec_bwd_d_out", "dec_bwd_w_out")
@@ -63,6 +76,13 @@ def parse_args(argv=None):
     ap.add_argument("--config", default="C2", help="BASELINE config id (C2 fp32 B=4096 default)")
     ap.add_argument("--batch", type=int, default=0, help="override per-GPU batch")
     ap.add_argument("--precision", default="", help="override GEMM arithmetic: f32 | f32x | bf16")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure: region pass and rooflines, "
+                         "rocprofv3 counter passes, CPU baseline and parity, h2d and input-pipeline "
+                         "legs, held-out overlap-MSE, the configs block")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the last timed step's outputs (losses, dist, grads, params) as "
+                         "DIR/<name>.npy")
     ap.add_argument("--cpu-seconds", type=float, default=3.0, help="per CPU-baseline timing leg")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-timing", action="store_true", help="disable per-region HIP events")
@@ -92,6 +112,12 @@ def parse_args(argv=None):
     args = ap.parse_args(argv)
     if args.region_steps < 1:
         ap.error("--region-steps must be >= 1 (the roofline's dominant kernel comes from the region pass)")
+    if args.mark_dominant and not args.full:
+        ap.error("--mark-dominant needs --full (the dominant region comes from the region pass)")
+    if not args.full:  # a plain run: the headline's timed steps only
+        args.no_timing = args.no_cpu_baseline = args.no_configs = True
+        args.no_h2d = args.no_pipeline = True
+        args.pmc = "off"
     return args
 
 
@@ -569,12 +595,37 @@ def allreduce_bench(eng, dev, world, dry_run, reps=5):
             "busbw_GBps": round(2 * (world - 1) / world * nbytes / (ms * 1e-3) / 1e9, 5)}
 
 
+def dump_outputs(d, eng, dry_run):
+    """``--dump-outputs``: what the last timed step left for the caller of the training step, one
+    ``<name>.npy`` each, in the buffers' own precision (float32; the dry run's stand-in float64):
+    ``losses`` (the 5 loss sums ``step`` returns), ``dist`` (the distance of every pair of the
+    batch), ``grads`` (the [g1 | g2] gradient buffer, all-reduced with N ranks) and ``params`` (the
+    parameters after the step's Adam updates). A buffer of more than DUMP_MAX_ELEMS values is
+    written as a sample of that many: the elements at the sorted indices
+    ``default_rng(DUMP_SEED).integers(0, size, DUMP_MAX_ELEMS)``, so at most 2 x 16 MB + the
+    small arrays reach the disk and two runs sample the same elements. Compare runs of one mode:
+    a ``--full`` run's region pass puts ``--region-steps`` more training steps before the timed
+    ones, so its last step is a later one than a plain run's."""
+    from magic_amd import _lib
+    os.makedirs(d, exist_ok=True)
+    arrays = {"losses": eng.losses, "dist": eng.dist, "grads": eng.grads}
+    if not dry_run:
+        arrays["params"] = eng.buffer(_lib.BUF_PARAMS)
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy().reshape(-1)
+        if a.size > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, a.size, DUMP_MAX_ELEMS))
+            a = a[idx]
+        np.save(os.path.join(d, name + ".npy"), a if a.dtype == np.float64 else a.astype(np.float32))
+
+
 def measure(args, cfg, world, rank, local, dev, *, timing, steps, warmup, keep=False, h2d=False,
-            pipeline=False):
-    """One configuration through the training step: W warm-up steps, a region pass (HIP events
-    around every region, outside the timed loop), K timed steps bracketed by barrier + device
-    sync (max over ranks), overlap-MSE on a held-out batch. h2d: a further timed loop in which
-    every step's X first comes from pinned host memory (copied on a side stream one step ahead,
+            pipeline=False, mse=True, dump_dir=""):
+    """One configuration through the training step: W warm-up steps, with timing a region pass
+    (HIP events around every region, outside the timed loop), K timed steps bracketed by barrier +
+    device sync (max over ranks), with dump_dir the last timed step's outputs written there by
+    rank 0 (dump_outputs), with mse the overlap-MSE on a held-out batch. h2d: a further timed
+    loop in which every step's X first comes from pinned host memory (copied on a side stream one step ahead,
     mirroring feed_dict, 11a/vae.py:399-402). pipeline: a further timed loop fed by the input
     pipeline itself -- inputs() over uint8 pair tables resident in HBM, each step's shuffled
     draw and rotation angles on the host, the batch assembled by the HIP producer
@@ -671,6 +722,8 @@ def measure(args, cfg, world, rank, local, dev, *, timing, steps, warmup, keep=F
     losses = eng.losses.cpu().numpy().tolist()
     if not np.all(np.isfinite(losses)):
         raise RuntimeError(f"non-finite losses after the timed steps: {losses}")
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, eng, args.dry_run)
     out = {"cfg": cfg, "elapsed": elapsed, "host_elapsed": host_t[0], "steps": steps,
            "regions": regions, "dom": dom,
            "dom_timed": dom_timed, "losses": losses, "comm": comm}
@@ -737,15 +790,16 @@ def measure(args, cfg, world, rank, local, dev, *, timing, steps, warmup, keep=F
                                    "input.py:127-261), rotation/interleave//255 by the HIP batch "
                                    "producer (mvae_make_batch), then the training step"}
     # overlap-MSE on a held-out seeded batch (11a/main.py:94-111; 1/pred for reciprocal)
-    if args.dry_run:
-        xe, ae = dry_run_batch(cfg, world, rank, 99)
-    else:
-        from magic_amd.overlap_input import synthetic_batch
-        xe, ae = synthetic_batch(cfg.batch, cfg.image_size, seed=999, device=dev)
-    pred = stepper.predict(xe).double()   # global-batch cosine norms under DP
-    if cfg.reciprocal:
-        pred = 1.0 / pred
-    out["mse"] = float(((pred - ae.double()) ** 2).mean().item())
+    if mse:
+        if args.dry_run:
+            xe, ae = dry_run_batch(cfg, world, rank, 99)
+        else:
+            from magic_amd.overlap_input import synthetic_batch
+            xe, ae = synthetic_batch(cfg.batch, cfg.image_size, seed=999, device=dev)
+        pred = stepper.predict(xe).double()   # global-batch cosine norms under DP
+        if cfg.reciprocal:
+            pred = 1.0 / pred
+        out["mse"] = float(((pred - ae.double()) ** 2).mean().item())
     if args.dry_run:
         w = torch.arange(1, eng.grads.numel() + 1, dtype=torch.float64)
         out["grad_checksum"] = float((eng.grads * w).sum())
@@ -993,7 +1047,8 @@ def main():
         return
 
     head = measure(args, cfg, world, rank, local, dev, timing=timing, steps=args.steps,
-                   warmup=args.warmup, keep=True, h2d=not args.no_h2d, pipeline=not args.no_pipeline)
+                   warmup=args.warmup, keep=True, h2d=not args.no_h2d, pipeline=not args.no_pipeline,
+                   mse=args.full, dump_dir=args.dump_outputs)
     eng = head.pop("eng")
     if rank == 0:
         print_regions(args, head, f"{args.config}")
@@ -1079,6 +1134,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": round(head["elapsed"] / args.steps * 1e3, 4),
             "host_ms_per_step": round(head["host_elapsed"] / args.steps * 1e3, 4),
             "higher_is_better": True,
@@ -1097,7 +1153,7 @@ def main():
                        "collective": ("gloo (dry run)" if args.dry_run else "RCCL all-reduce")
                        if world > 1 else None},
             "per_gpu_value": round(value / world, 2),
-            "overlap_mse": round(head["mse"], 2),
+            "overlap_mse": round(head["mse"], 2) if "mse" in head else None,
             "losses": {"cost": losses[0], "training_loss": losses[1], "r_l": losses[2],
                        "l_l": losses[3], "d_l": losses[4]},
             "roofline": roofline,

@@ -22,8 +22,8 @@ def _run(*args):
 
 
 def test_bench_self_launches_two_ranks_and_matches_one():
-    two = _run("--gpus", "2", "--batch", "8", "--steps", "3", "--warmup", "1")
-    one = _run("--gpus", "1", "--batch", "16", "--steps", "3", "--warmup", "1")
+    two = _run("--full", "--gpus", "2", "--batch", "8", "--steps", "3", "--warmup", "1")
+    one = _run("--full", "--gpus", "1", "--batch", "16", "--steps", "3", "--warmup", "1")
     assert two["n_gpus"] == 2 and one["n_gpus"] == 1
     assert two["config"]["global_batch"] == 16 and two["config"]["per_gpu_batch"] == 8
     assert two["config"]["parallelism"] == "dp2" and two["scaling"] == "weak"
@@ -53,3 +53,32 @@ def test_bench_self_launches_two_ranks_and_matches_one():
             assert k in c, k
         assert c["bucket_bytes"] > 0 and c["steps"] == 3 and c["world"] == 2
         assert c["allreduce_bench"]["busbw_GBps"] > 0
+
+
+def test_plain_run_times_the_steps_and_dumps_its_outputs(tmp_path):
+    """Without ``--full`` the run is the headline alone (every other block of the line is empty),
+    ``--steps`` is the number of timed steps, and ``--dump-outputs`` writes the last step's
+    outputs: float arrays, at most 64 MB in all, identical from run to run."""
+    import numpy as np
+    lines, dumps = [], []
+    for tag in ("a", "b"):
+        d = tmp_path / tag
+        lines.append(_run("--gpus", "1", "--batch", "16", "--steps", "4", "--warmup", "1",
+                          "--dump-outputs", str(d)))
+        dumps.append({p.name: np.load(p) for p in sorted(d.iterdir())})
+    line = lines[0]
+    assert line["full"] is False and line["steps"] == 4 and line["warmup"] == 1
+    assert line["ms_per_step"] > 0 and line["higher_is_better"] is True
+    assert abs(line["value"] - 16 / (line["ms_per_step"] * 1e-3)) <= 1e-3 * line["value"]
+    assert line["configs"] == {}
+    for k in ("roofline", "loss_roofline", "cpu_baseline", "h2d", "pipeline", "overlap_mse"):
+        assert line[k] is None, k
+    a, b = dumps
+    assert set(a) == set(b) and {"losses.npy", "dist.npy", "grads.npy"} <= set(a)
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64) and a[k].size > 0
+        assert np.array_equal(a[k], b[k]), k
+    # the dump is the last timed step's: its losses are the line's
+    assert a["losses.npy"].tolist() == [line["losses"][k] for k in
+                                        ("cost", "training_loss", "r_l", "l_l", "d_l")]

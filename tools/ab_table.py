@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Tabulate bench.py A/B runs: pairs/s, ms/step and chosen region times of each
+"""Tabulate bench.py --full A/B runs: pairs/s, ms/step and chosen region times of each
 gpurun_out/<name>.json / .err pair.  usage: python tools/ab_table.py NAME... [--keys a,b,c]"""
 import json
 import re

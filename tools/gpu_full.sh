@@ -31,13 +31,13 @@ python3 $R/tools/pmc_traffic.py --fetch $O/pmc_fetch_$TAG --write $O/pmc_write_$
     --config ${CFG:-C2} --precision ${PREC:-f32x} > $O/pmc_traffic_$TAG.json || exit 1
 cat $O/pmc_traffic_$TAG.json
 run prof_$TAG 300 rocprofv3 --kernel-trace --stats -T --output-format csv -d $O/prof_$TAG -o run -- \
-    python3 $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline ${BENCH_ARGS}
+    python3 $R/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline ${BENCH_ARGS}
 cd $R
 python3 tools/summarize_prof.py "$(find $O/prof_$TAG -name "*kernel_trace.csv" | sort | tail -n 1)" > $O/prof_${TAG}_summary.md || exit 1
-run bench_$TAG 600 python bench.py --traffic-json $O/pmc_traffic_$TAG.json ${BENCH_ARGS}
+run bench_$TAG 600 python bench.py --full ${BENCH_ARGS}
 grep '^{' $O/bench_$TAG.log
 if [ -n "$EXTRA_BENCH" ]; then
-  run bench_${TAG}_extra 300 python bench.py --no-cpu-baseline $EXTRA_BENCH
+  run bench_${TAG}_extra 300 python bench.py --full --no-cpu-baseline $EXTRA_BENCH
   grep '^{' $O/bench_${TAG}_extra.log
 fi
 echo "[gpu_full] done"

@@ -21,12 +21,12 @@ if [ -z "$SKIP_TESTS" ]; then
   [ $rc -gt 1 ] && exit $rc
   step smoke 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke_$TAG.log 2>&1 || exit $?
 fi
-step bench 900 python bench.py ${BENCH_ARGS} > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err || { tail -20 $OUT/bench_$TAG.err; exit 3; }
+step bench 900 python bench.py --full ${BENCH_ARGS} > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err || { tail -20 $OUT/bench_$TAG.err; exit 3; }
 cat $OUT/bench_$TAG.json
 if [ -z "$SKIP_PROF" ]; then
   export TMPDIR=/tmp
   cd /tmp
   step rocprof 600 rocprofv3 --kernel-trace --stats -T --output-format csv -d $OUT/prof_$TAG -o run -- \
-      python3 $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline ${BENCH_ARGS} > $OUT/prof_$TAG.log 2>&1 || exit $?
+      python3 $R/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline ${BENCH_ARGS} > $OUT/prof_$TAG.log 2>&1 || exit $?
 fi
 echo "[gpu_round] done"

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """The timed loop's steps in a rocprofv3 kernel trace of one bench.py configuration
-(``bench.py --config X --no-configs ...``): per launch of a step -- keyed by (kernel, workgroups,
+(``bench.py --full --config X --no-configs ...``): per launch of a step -- keyed by (kernel, workgroups,
 occurrence within the step), so the side stream's interleaving does not matter -- the mean start
 offset and duration over the timed steps, in launch order; and, with ``--mark-dominant`` runs,
 the kernels between each pair of region markers summed per step (the dominant region's launches

@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define MVAE_ABI_VERSION 4
+#define MVAE_ABI_VERSION 5
 #define MVAE_MAX_ENC 8
 
 enum { MVAE_OK = 0, MVAE_EINVAL = -1, MVAE_ECONFIG = -2, MVAE_ESTATE = -3 };
@@ -245,6 +245,42 @@ int mvae_make_batch(const unsigned char* locks, const unsigned char* keys, int h
                     const int* idx, const float* coef, int batch, float divisor, float* x_out,
                     void* stream);
 
+/* ---- a batch described by its sources: no X ---------------------------------------- */
+/* The batch mvae_make_batch would write, described instead of materialised: the uint8 tables
+ * that already live in HBM, the example of each row and its rotation. Every entry point that takes
+ * x has a *_pairs twin taking this descriptor; its results are bitwise those of mvae_make_batch
+ * into an x followed by the x call, in every configuration.
+ *
+ * Direct path: where the context de-interleaves a 0/1 batch to bits in a launch of its own (bf16 /
+ * f32x precision with the default "bits" and "e8" plans, FC encoder, batch % 64 == 0,
+ * image_size^2 % 8 == 0, no deint_fuse and no diag_* option) and both tables are 8-byte aligned,
+ * one kernel writes the layer-0 bit operands straight from the tables (timing region
+ * "pairs_bits"): 2 table bytes read per pixel triple instead of 12 bytes of X written and read
+ * back. In every other configuration the twin materialises X into a context-owned [B, 3 D] fp32
+ * scratch (allocated at the first such call, never at create) and runs the x code on it.
+ *
+ * Preconditions as for mvae_make_batch: every idx[b] in [0, n) (not checked: the kernels index the
+ * tables with it), coef 16-byte aligned. height / width other than cfg.image_size, a null pointer,
+ * a misaligned coef or a divisor <= 0 is MVAE_EINVAL with a message. The tables, idx and coef are
+ * read by the kernels the call enqueues: keep them unchanged until those have run.             */
+typedef struct mvae_pairs {
+  const unsigned char *locks, *keys;  /* device, uint8 [n][H][W]                      */
+  int height, width;                  /* must equal cfg.image_size                    */
+  const int* idx;                     /* device int32 [B], each in [0, n)             */
+  const float* coef;                  /* device float [B][4], 16-byte aligned         */
+  float divisor;                      /* 255 (normalize) or 1                         */
+} mvae_pairs;
+int mvae_forward_pairs(mvae_ctx* ctx, const mvae_pairs* pairs, const float* eps, void* stream);
+int mvae_train_step_pairs(mvae_ctx* ctx, const mvae_pairs* pairs, const float* areas, const float* eps,
+                          float* losses_out, float* dist_out, void* stream);
+int mvae_predict_pairs(mvae_ctx* ctx, const mvae_pairs* pairs, const float* eps, float* dist_out,
+                       void* stream);
+/* (followed by mvae_predict_finish, as mvae_predict_encode) */
+int mvae_predict_encode_pairs(mvae_ctx* ctx, const mvae_pairs* pairs, const float* eps, void* stream);
+int mvae_transform_pairs(mvae_ctx* ctx, const mvae_pairs* pairs, float* zmean_out, void* stream);
+int mvae_reconstruct_pairs(mvae_ctx* ctx, const mvae_pairs* pairs, const float* eps, float* y_out,
+                           void* stream);
+
 /* ---- diagnostics ------------------------------------------------------------------ */
 /* HIP-event timing of named regions (one GEMM incl. its split-K reduction, or one
  * bandwidth kernel group), recorded on the launch stream while enabled.               */
@@ -279,6 +315,18 @@ int mvae_bench_deint(int B, int D, int variant, int iters, void* stream, float* 
  * activation (4B). mfma: bf16 MFMA kernels (operands rounded to bf16), else fp32 VALU.     */
 int mvae_debug_conv2(int S1, int B, int mode, int mfma, const float* x, const float* y, float* out,
                      void* stream);
+/* The bit operands of a batch of S x S images on caller buffers (tests; synchronous; allocates
+ * nothing). mode 0: mvae_make_batch into x [B][3 S S], then the step's de-interleave to bits;
+ * mode 1: the direct kernel of the *_pairs entry points. no_xbw: the forward words only (the
+ * xbw_split schedule). Outputs, zero-filled by the caller (padding is never written): xbf
+ * ceil(3B/256) ceil((D+1)/64) 512 words, xbw ceil((D+1)/256) ceil(3B/64) 512 words, xbits
+ * [B][ldbits] bytes, dyn 4 ints (slot 0: words 0 inexact, 2 not-binary), and -- written only when
+ * the not-binary word rises -- plane 0 of the bf16 image plane [3B][ldx]. B % 64 == 0,
+ * S S % 8 == 0, ldx % 8 == 0, tables 8-byte and coef 16-byte aligned, else MVAE_EINVAL.        */
+int mvae_debug_pairs_bits(const unsigned char* locks, const unsigned char* keys, const int* idx,
+                          const float* coef, int B, int S, float divisor, int mode, int no_xbw, float* x,
+                          unsigned* xbf, unsigned* xbw, unsigned char* xbits, int ldbits, int* dyn,
+                          unsigned short* plane, int ldx, void* stream);
 int mvae_debug_gemm(int M, int N, int K, const float* A, int lda, int at, const float* B, int ldb,
                     int bt, float* C, int ldc, int epi, int act, const float* aux, int ld_aux,
                     void* stream);

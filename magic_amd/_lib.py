@@ -14,7 +14,7 @@ LIB_PATH = os.environ.get("MVAE_LIB", os.path.join(HERE, "libmvae.so"))
 
 MVAE_MAX_ENC = 8
 MARKER_GRID = 4096   # mvae_region_marker workgroups = MARKER_GRID + region (mvae_internal.h)
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 ACT = {"tanh": 0, "elu": 1}
 METRIC = {"cosine": 0, "sqdiff": 1}
@@ -44,6 +44,12 @@ class mvae_cfg(C.Structure):
         ("beta1", C.c_float), ("beta2", C.c_float), ("epsilon", C.c_float),
         ("precision", C.c_int), ("seed", C.c_uint64), ("conv", C.c_int),
     ]
+
+
+class mvae_pairs(C.Structure):
+    """A batch described by its sources (``include/mvae.h``): device pointers and sizes."""
+    _fields_ = [("locks", C.c_void_p), ("keys", C.c_void_p), ("height", C.c_int), ("width", C.c_int),
+                ("idx", C.c_void_p), ("coef", C.c_void_p), ("divisor", C.c_float)]
 
 
 class mvae_tensor(C.Structure):
@@ -85,6 +91,14 @@ _SIGS = {
     "mvae_generate": ([C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p], C.c_int),
     "mvae_make_batch": ([C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                          C.c_float, C.c_void_p, C.c_void_p], C.c_int),
+    "mvae_forward_pairs": ([C.c_void_p, C.POINTER(mvae_pairs), C.c_void_p, C.c_void_p], C.c_int),
+    "mvae_train_step_pairs": ([C.c_void_p, C.POINTER(mvae_pairs), C.c_void_p, C.c_void_p, C.c_void_p,
+                               C.c_void_p, C.c_void_p], C.c_int),
+    "mvae_predict_pairs": ([C.c_void_p, C.POINTER(mvae_pairs), C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+    "mvae_predict_encode_pairs": ([C.c_void_p, C.POINTER(mvae_pairs), C.c_void_p, C.c_void_p], C.c_int),
+    "mvae_transform_pairs": ([C.c_void_p, C.POINTER(mvae_pairs), C.c_void_p, C.c_void_p], C.c_int),
+    "mvae_reconstruct_pairs": ([C.c_void_p, C.POINTER(mvae_pairs), C.c_void_p, C.c_void_p, C.c_void_p],
+                               C.c_int),
     "mvae_timing_enable": ([C.c_void_p, C.c_int], C.c_int),
     "mvae_timing_select": ([C.c_void_p, C.c_int], C.c_int),
     "mvae_timing_marker": ([C.c_void_p, C.c_int, C.c_int], C.c_int),
@@ -97,6 +111,9 @@ _SIGS = {
     "mvae_bench_deint": ([C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_float)], C.c_int),
     "mvae_debug_conv2": ([C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                           C.c_void_p], C.c_int),
+    "mvae_debug_pairs_bits": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float,
+                               C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                               C.c_void_p, C.c_void_p, C.c_int, C.c_void_p], C.c_int),
     "mvae_debug_gemm": ([C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                          C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                          C.c_int, C.c_void_p], C.c_int),

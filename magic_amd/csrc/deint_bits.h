@@ -93,6 +93,88 @@ __device__ __forceinline__ void deint_load_co(const float4* __restrict__ x, int 
   }
 }
 
+// bf16 bits of v rounded to nearest even, and the exact remainder v - bf16(v)
+__device__ __forceinline__ unsigned short bf16_rn(float v, float& rem) {
+  const unsigned short b = __builtin_bit_cast(unsigned short, __float2bfloat16(v));
+  rem = v - __uint_as_float((unsigned)b << 16);
+  return b;
+}
+__device__ __forceinline__ uint2 pack4(unsigned short a, unsigned short b, unsigned short c,
+                                       unsigned short d) {
+  return make_uint2((unsigned)a | (unsigned)b << 16, (unsigned)c | (unsigned)d << 16);
+}
+
+// 4 NQ pixels (3 NQ float4 of x in v, pixel order) of row b from column col -> the fp32 rows
+// of the blocks in f32mask and bf16 plane 0 (16-B stores); returns whether a pixel is inexact
+template <int NQ>
+__device__ __forceinline__ bool deint_put(const float4* v, float* __restrict__ xs,
+                                          unsigned short* __restrict__ xp, int B, int b,
+                                          size_t col, int ldx, int f32mask) {
+  static_assert(NQ % 2 == 0, "whole 16-B plane stores");
+  constexpr int NP = 4 * NQ;
+  bool nz = false;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const int ch = c == 0 ? 1 : (c == 1 ? 0 : 2);  // block c (rot, lock, key) <- channel ch
+    float f[NP];
+#pragma unroll
+    for (int h = 0; h < NQ; ++h) {
+      const float4 a = v[3 * h], bb = v[3 * h + 1], cc = v[3 * h + 2];
+      const float e[12] = {a.x, a.y, a.z, a.w, bb.x, bb.y, bb.z, bb.w, cc.x, cc.y, cc.z, cc.w};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) f[4 * h + j] = e[3 * j + ch];
+    }
+    const size_t o = (size_t)(c * B + b) * ldx + col;
+    if (f32mask >> c & 1) {
+#pragma unroll
+      for (int h = 0; h < NQ; ++h)
+        *reinterpret_cast<float4*>(xs + o + 4 * h) = make_float4(f[4 * h], f[4 * h + 1], f[4 * h + 2], f[4 * h + 3]);
+    }
+    if (xp) {
+#pragma unroll
+      for (int h = 0; h < NQ; h += 2) {
+        float r[8];
+        unsigned short h16[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) h16[j] = bf16_rn(f[4 * h + j], r[j]);
+        const uint2 lo = pack4(h16[0], h16[1], h16[2], h16[3]), hi = pack4(h16[4], h16[5], h16[6], h16[7]);
+        *reinterpret_cast<uint4*>(xp + o + 4 * h) = make_uint4(lo.x, lo.y, hi.x, hi.y);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) nz |= r[j] != 0.f;
+      }
+    }
+  }
+  return nz;
+}
+
+// The grey pass's work on pixel octet q of batch row b (v: its 24 values as X stores them): bf16
+// plane 0 and the fp32 rows of the blocks in f32mask (deint_put), planes 1-2 of the exact split
+// when np == 3; returns whether a pixel is inexact in bf16. Shared by deint_grey_kernel (v read
+// from X) and pairs_grey_kernel (v rebuilt from the uint8 tables).
+__device__ __forceinline__ bool deint_grey_octet(const float4 (&v)[6], float* __restrict__ xs,
+                                                 unsigned short* __restrict__ xp, long long ps, int np,
+                                                 int f32mask, int B, int b, int q, int ldx) {
+  const bool nz = deint_put<2>(v, xs, xp, B, b, (size_t)8 * q, ldx, f32mask);
+  if (np == 3) {  // the exact split's residual planes of the 24 values
+    const float e[24] = {v[0].x, v[0].y, v[0].z, v[0].w, v[1].x, v[1].y, v[1].z, v[1].w,
+                         v[2].x, v[2].y, v[2].z, v[2].w, v[3].x, v[3].y, v[3].z, v[3].w,
+                         v[4].x, v[4].y, v[4].z, v[4].w, v[5].x, v[5].y, v[5].z, v[5].w};
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const int ch = c == 0 ? 1 : (c == 1 ? 0 : 2);
+      const size_t o = (size_t)(c * B + b) * ldx + (size_t)8 * q;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        float r1, r2, r3;
+        (void)bf16_rn(e[3 * j + ch], r1);
+        xp[ps + o + j] = bf16_rn(r1, r2);
+        xp[2 * ps + o + j] = bf16_rn(r2, r3);
+      }
+    }
+  }
+  return nz;
+}
+
 // one row's 8 pixels x 3 channels (interleaved, as X stores them) -> the byte of each block
 // (bit j = pixel j nonzero; block c: rot, lock, key <- channels 1, 0, 2); true if a value is not
 // 0 / 1
@@ -170,6 +252,46 @@ __device__ __forceinline__ void deint_words(int t0, int nt, int B, int D, int kt
   }
 }
 
+// One octet of one task row into the task's LDS bytes: its three block bytes from the 24 values e
+// (an octet inside the image, `in`; then also the row's target byte into xbits) or the padding byte
+// `pad` (the ones column at pixel D, zeros past it); returns whether a value is not 0 / 1. Where
+// the 24 values come from is the caller's business: X (deint_finish) or the uint8 tables
+// (pairs_bits.hip).
+template <int PB, int OS>
+__device__ __forceinline__ bool deint_octet_put(bool in, unsigned pad, const float (&e)[24],
+                                                unsigned char* __restrict__ xbits_at, DeintLds<PB, OS>& bt, int o,
+                                                int r) {
+  bool nb = false;
+  unsigned by3[3] = {pad, pad, pad};
+  if (in) {
+    nb = deint_octet(e, by3);
+    *xbits_at = (unsigned char)by3[1];
+  }
+#pragma unroll
+  for (int c = 0; c < 3; ++c) bt[c][o][r] = (unsigned char)by3[c];
+  return nb;
+}
+// the ones column (pixel D) and zeros of an octet at pixel pix that is not whole inside the image
+__device__ __forceinline__ unsigned deint_pad(int pix, int D) {
+  return (pix <= D && D < pix + 8) ? 1u << (D - pix) : 0u;
+}
+// The rest of a task once every thread has put its octets (nb: this thread saw a value not 0 / 1):
+// the not-binary word, the workgroup's synchronisation, the BitMat words
+template <int PB, int NT, int OS, bool SC1, class FW, class FS, bool NOW = false>
+__device__ __forceinline__ void deint_tail(bool nb, int B, int D, int kts_f, int kts_w, unsigned* __restrict__ xbf,
+                                           unsigned* __restrict__ xbw, int* __restrict__ dyn, int bx, int by,
+                                           const DeintLds<PB, OS>& bt, FW&& written, FS&& synced) {
+  const int tid = threadIdx.x;
+  written();
+  if (dyn) {
+    const bool anb = __ballot(nb) != 0;
+    if ((tid & 63) == 0 && anb) atomicOr(dyn + 2, 1);
+  }
+  __syncthreads();
+  synced();
+  deint_words<PB, OS, SC1, NOW>(tid, NT, B, D, kts_f, kts_w, xbf, xbw, bx, by, bt);
+}
+
 template <int PB, int NT, int OS, bool SC1, class FW, class FS, bool NOW = false>
 __device__ __forceinline__ void deint_finish(int B, int D, int kts_f, int kts_w, unsigned* __restrict__ xbf,
                                              unsigned* __restrict__ xbw, unsigned char* __restrict__ xbits,
@@ -183,30 +305,16 @@ __device__ __forceinline__ void deint_finish(int B, int D, int kts_f, int kts_w,
   const int o = tid % NO, pix = p0 + 8 * o;
   const bool in = pix + 8 <= D;
   bool nb = false;
-  // pixels past D: the ones column (pixel D) and zeros
-  const unsigned pad = (pix <= D && D < pix + 8) ? 1u << (D - pix) : 0u;
+  const unsigned pad = deint_pad(pix, D);
 #pragma unroll
   for (int i = 0; i < NR; ++i) {
     const int r = tid / NO + RPP * i;
-    unsigned by3[3] = {pad, pad, pad};
-    if (in) {
-      const float e[24] = {v[i][0].x, v[i][0].y, v[i][0].z, v[i][0].w, v[i][1].x, v[i][1].y, v[i][1].z, v[i][1].w,
-                           v[i][2].x, v[i][2].y, v[i][2].z, v[i][2].w, v[i][3].x, v[i][3].y, v[i][3].z, v[i][3].w,
-                           v[i][4].x, v[i][4].y, v[i][4].z, v[i][4].w, v[i][5].x, v[i][5].y, v[i][5].z, v[i][5].w};
-      nb |= deint_octet(e, by3);
-      xbits[(size_t)(b0 + r) * ldbits + (pix >> 3)] = (unsigned char)by3[1];
-    }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) bt[c][o][r] = (unsigned char)by3[c];
+    const float e[24] = {v[i][0].x, v[i][0].y, v[i][0].z, v[i][0].w, v[i][1].x, v[i][1].y, v[i][1].z, v[i][1].w,
+                         v[i][2].x, v[i][2].y, v[i][2].z, v[i][2].w, v[i][3].x, v[i][3].y, v[i][3].z, v[i][3].w,
+                         v[i][4].x, v[i][4].y, v[i][4].z, v[i][4].w, v[i][5].x, v[i][5].y, v[i][5].z, v[i][5].w};
+    nb |= deint_octet_put<PB, OS>(in, pad, e, xbits + (size_t)(b0 + r) * ldbits + (pix >> 3), bt, o, r);
   }
-  written();
-  if (dyn) {
-    const bool anb = __ballot(nb) != 0;
-    if ((tid & 63) == 0 && anb) atomicOr(dyn + 2, 1);
-  }
-  __syncthreads();
-  synced();
-  deint_words<PB, OS, SC1, NOW>(tid, NT, B, D, kts_f, kts_w, xbf, xbw, bx, by, bt);
+  deint_tail<PB, NT, OS, SC1, FW, FS, NOW>(nb, B, D, kts_f, kts_w, xbf, xbw, dyn, bx, by, bt, written, synced);
 }
 
 // the whole task (the standalone kernel's workgroup)

@@ -49,6 +49,9 @@ struct mvae_ctx {
   bool stage_pending = false;
   unsigned short* shadow = nullptr;
   const float* last_x = nullptr;
+  // a batch given as (tables, idx, coefficients) (the *_pairs entry points) where the direct
+  // kernel does not apply: X materialised here (launch_make_batch), allocated on first need
+  float* pairs_x = nullptr;
   int B = 0, D = 0, L = 0, nenc = 0, d0 = 0, d1 = 0;
   float inv_bg = 1.f;
   int ldx = 0, ldz = 0, ld_d1 = 0, ld_d2 = 0, ld_u = 0, lddz = 0, ld_dh = 0, nblk = 0, nchunk = 0;
@@ -1324,9 +1327,15 @@ enum { ENC_TRAIN = 0, ENC_EVAL = 1, ENC_MEAN = 2 };
 
 static int shadow_deint(mvae_ctx* ctx, hipStream_t st);
 
-static int encode(mvae_ctx* ctx, const float* x, const float* eps, hipStream_t st, int draw = ENC_TRAIN) {
+// The batch is x, or (x == NULL) the pairs descriptor. A pairs batch takes the direct kernel
+// (launch_pairs_bits: the BitMats straight from the tables) exactly where an x batch would take the
+// plain bits branch below and the launcher's shape / alignment conditions hold; in every other
+// configuration X is materialised into the context's scratch and the x code runs on it.
+static int encode(mvae_ctx* ctx, const float* x, const float* eps, hipStream_t st, int draw = ENC_TRAIN,
+                  const mvae_pairs* pairs = nullptr) {
   auto c = ctx;
-  c->last_x = x;
+  const bool direct = pairs && c->bits_on && !c->fuse && !c->diag_skip_deint && !c->diag_shadow &&
+                      pairs_bits_fits(pairs->locks, pairs->keys, pairs->coef, c->B, c->D);
   if (c->side && c->side_pending) {  // an early-Adam backward whose mvae_adam never came
     c->side_pending = false;
     c->early_fork = false;
@@ -1342,6 +1351,19 @@ static int encode(mvae_ctx* ctx, const float* x, const float* eps, hipStream_t s
     MV_CHECK(hipEventRecord(c->sync_ev[c->sync_next % c->sync_ev.size()], c->stage));
     MV_CHECK(hipStreamWaitEvent(st, c->sync_ev[c->sync_next++ % c->sync_ev.size()], 0));
   }
+  if (pairs && !direct) {
+    if (!c->pairs_x) {
+      void* q = nullptr;
+      MV_CHECK(hipMalloc(&q, (size_t)c->B * 3 * c->D * sizeof(float)));
+      c->allocs.push_back(q);
+      c->pairs_x = static_cast<float*>(q);
+    }
+    TIMED("pairs_make_batch");
+    MV_CHECK(launch_make_batch(pairs->locks, pairs->keys, pairs->height, pairs->width, pairs->idx, pairs->coef,
+                               c->B, pairs->divisor, c->pairs_x, st));
+    x = c->pairs_x;
+  }
+  c->last_x = x;
   bool f0_done = false;  // the layer-0 forward ran with the fused de-interleave
   if (c->fuse && !c->diag_skip_deint && !c->diag_shadow && (reinterpret_cast<uintptr_t>(x) % 16) == 0) {
     // one launch: the de-interleave's workers beside the forward GEMM's tiles (DeintJob); then the
@@ -1371,16 +1393,21 @@ static int encode(mvae_ctx* ctx, const float* x, const float* eps, hipStream_t s
     c->dyn_cur = cur;
     f0_done = true;
   } else if (!(c->diag_skip_deint && c->dyn_cur)) {  // (diagnostics: the stale image of the last pass)
-    TIMED("deinterleave");
+    TimeScope ts_deint(ctx, region(ctx, direct ? "pairs_bits" : "deinterleave"), st);
     // the flag's slots alternate: this pass raises the one the previous pass zeroed and zeroes
     // the previous one (its readers are all behind on this stream), no memset launch per step
     int* prev = c->dyn_cur ? c->dyn_cur : c->dyn;
     int* cur = c->dyn ? (prev == c->dyn ? c->dyn + 1 : c->dyn) : nullptr;
     if (c->bits_on) {  // the BitMats and target bits; the planes only for a batch not all 0 / 1
       const bool split = c->xbw_split && draw == ENC_TRAIN;  // (eval passes need no xbw)
-      MV_CHECK(launch_deint_bits(x, c->B, c->D, c->xbf, c->kts_f, c->xbw, c->kts_w, c->xbits, c->ldbits, cur,
-                                 prev, c->xs, planes_of(c, c->xs), c->ldx, c->x32dyn, st,
-                                 split ? (c->deint_variant == 8 ? 9 : 7) : c->deint_variant));
+      if (direct)
+        MV_CHECK(launch_pairs_bits(pairs->locks, pairs->keys, pairs->height, pairs->width, pairs->idx, pairs->coef,
+                                   pairs->divisor, c->B, c->xbf, c->kts_f, c->xbw, c->kts_w, c->xbits, c->ldbits,
+                                   cur, prev, c->xs, planes_of(c, c->xs), c->ldx, c->x32dyn, split, st));
+      else
+        MV_CHECK(launch_deint_bits(x, c->B, c->D, c->xbf, c->kts_f, c->xbw, c->kts_w, c->xbits, c->ldbits, cur,
+                                   prev, c->xs, planes_of(c, c->xs), c->ldx, c->x32dyn, st,
+                                   split ? (c->deint_variant == 8 ? 9 : 7) : c->deint_variant));
       if (split) {  // xbw from xbf on the side stream, beside the layer-0 forward
         const bool two = c->use_side && c->side;
         hipStream_t sd = two ? c->side : st;
@@ -1472,10 +1499,23 @@ static int decode_hidden(mvae_ctx* ctx, hipStream_t st) {
   return rc ? rc : run(ctx, ctx->f_d2, st, ctx->f_d2_r);
 }
 
-extern "C" int mvae_forward(mvae_ctx* ctx, const float* x, const float* eps, void* stream) {
-  if (!ctx || !x) return MVAE_EINVAL;
+// a pairs descriptor's arguments (idx's range is the caller's precondition, as for mvae_make_batch)
+static int check_pairs(mvae_ctx* ctx, const mvae_pairs* p, const char* who) {
+  const std::string w(who);
+  if (!p || !p->locks || !p->keys || !p->idx || !p->coef)
+    return fail(ctx, MVAE_EINVAL, w + ": null pairs descriptor, table, idx or coef");
+  if (p->height != ctx->cfg.image_size || p->width != ctx->cfg.image_size)
+    return fail(ctx, MVAE_EINVAL, w + ": tables are " + std::to_string(p->height) + " x " + std::to_string(p->width) +
+                                      ", the context's image_size is " + std::to_string(ctx->cfg.image_size));
+  if ((reinterpret_cast<uintptr_t>(p->coef) & 15) != 0)
+    return fail(ctx, MVAE_EINVAL, w + ": coef must be 16-byte aligned");
+  if (!(p->divisor > 0.f)) return fail(ctx, MVAE_EINVAL, w + ": divisor must be positive");
+  return MVAE_OK;
+}
+
+static int forward_any(mvae_ctx* ctx, const float* x, const mvae_pairs* pairs, const float* eps, void* stream) {
   hipStream_t st = (hipStream_t)stream;
-  int rc = encode(ctx, x, eps, st);
+  int rc = encode(ctx, x, eps, st, ENC_TRAIN, pairs);
   if (rc) return rc;
   if ((rc = decode_hidden(ctx, st))) return rc;
   if (ctx->f_split && ctx->use_split) {
@@ -1486,6 +1526,17 @@ extern "C" int mvae_forward(mvae_ctx* ctx, const float* x, const float* eps, voi
   }
   ctx->phase = 1;
   return MVAE_OK;
+}
+
+extern "C" int mvae_forward(mvae_ctx* ctx, const float* x, const float* eps, void* stream) {
+  if (!ctx || !x) return MVAE_EINVAL;
+  return forward_any(ctx, x, nullptr, eps, stream);
+}
+
+extern "C" int mvae_forward_pairs(mvae_ctx* ctx, const mvae_pairs* pairs, const float* eps, void* stream) {
+  if (!ctx) return MVAE_EINVAL;
+  if (int rc = check_pairs(ctx, pairs, "mvae_forward_pairs")) return rc;
+  return forward_any(ctx, nullptr, pairs, eps, stream);
 }
 
 extern "C" int mvae_metric(mvae_ctx* ctx, const float* areas, void* stream) {
@@ -1824,11 +1875,10 @@ extern "C" int mvae_adam(mvae_ctx* ctx, void* stream) {
   return MVAE_OK;
 }
 
-extern "C" int mvae_train_step(mvae_ctx* ctx, const float* x, const float* areas, const float* eps,
-                               float* losses_out, float* dist_out, void* stream) {
-  if (!ctx || !x || !areas) return MVAE_EINVAL;
+static int train_step_any(mvae_ctx* ctx, const float* x, const mvae_pairs* pairs, const float* areas,
+                          const float* eps, float* losses_out, float* dist_out, void* stream) {
   int rc;
-  if ((rc = mvae_forward(ctx, x, eps, stream))) return rc;
+  if ((rc = forward_any(ctx, x, pairs, eps, stream))) return rc;
   if ((rc = mvae_metric(ctx, areas, stream))) return rc;
   hipStream_t st = (hipStream_t)stream;
   if (losses_out) MV_CHECK(hipMemcpyAsync(losses_out, ctx->losses, 5 * sizeof(float), hipMemcpyDeviceToDevice, st));
@@ -1844,14 +1894,38 @@ extern "C" int mvae_train_step(mvae_ctx* ctx, const float* x, const float* areas
   return mvae_adam(ctx, stream);
 }
 
+extern "C" int mvae_train_step(mvae_ctx* ctx, const float* x, const float* areas, const float* eps,
+                               float* losses_out, float* dist_out, void* stream) {
+  if (!ctx || !x || !areas) return MVAE_EINVAL;
+  return train_step_any(ctx, x, nullptr, areas, eps, losses_out, dist_out, stream);
+}
+
+extern "C" int mvae_train_step_pairs(mvae_ctx* ctx, const mvae_pairs* pairs, const float* areas, const float* eps,
+                                     float* losses_out, float* dist_out, void* stream) {
+  if (!ctx || !areas) return MVAE_EINVAL;
+  if (int rc = check_pairs(ctx, pairs, "mvae_train_step_pairs")) return rc;
+  return train_step_any(ctx, nullptr, pairs, areas, eps, losses_out, dist_out, stream);
+}
+
 // get_predictions in two phases (a data-parallel host all-reduces MVAE_BUF_COLSQ between them:
 // the cosine distance normalises over the GLOBAL batch, 8c/vae.py:449-450)
-extern "C" int mvae_predict_encode(mvae_ctx* ctx, const float* x, const float* eps, void* stream) {
-  if (!ctx || !x) return MVAE_EINVAL;
-  int rc = encode(ctx, x, eps, (hipStream_t)stream, ENC_EVAL);
+static int predict_encode_any(mvae_ctx* ctx, const float* x, const mvae_pairs* pairs, const float* eps,
+                              void* stream) {
+  int rc = encode(ctx, x, eps, (hipStream_t)stream, ENC_EVAL, pairs);
   if (rc) return rc;
   ctx->phase = 6;
   return MVAE_OK;
+}
+
+extern "C" int mvae_predict_encode(mvae_ctx* ctx, const float* x, const float* eps, void* stream) {
+  if (!ctx || !x) return MVAE_EINVAL;
+  return predict_encode_any(ctx, x, nullptr, eps, stream);
+}
+
+extern "C" int mvae_predict_encode_pairs(mvae_ctx* ctx, const mvae_pairs* pairs, const float* eps, void* stream) {
+  if (!ctx) return MVAE_EINVAL;
+  if (int rc = check_pairs(ctx, pairs, "mvae_predict_encode_pairs")) return rc;
+  return predict_encode_any(ctx, nullptr, pairs, eps, stream);
 }
 
 extern "C" int mvae_predict_finish(mvae_ctx* ctx, float* dist_out, void* stream) {
@@ -1872,10 +1946,16 @@ extern "C" int mvae_predict(mvae_ctx* ctx, const float* x, const float* eps, flo
   return rc ? rc : mvae_predict_finish(ctx, dist_out, stream);
 }
 
-extern "C" int mvae_transform(mvae_ctx* ctx, const float* x, float* zmean_out, void* stream) {
-  if (!ctx || !x || !zmean_out) return MVAE_EINVAL;
+extern "C" int mvae_predict_pairs(mvae_ctx* ctx, const mvae_pairs* pairs, const float* eps, float* dist_out,
+                                  void* stream) {
+  if (!ctx || !dist_out) return MVAE_EINVAL;
+  int rc = mvae_predict_encode_pairs(ctx, pairs, eps, stream);
+  return rc ? rc : mvae_predict_finish(ctx, dist_out, stream);
+}
+
+static int transform_any(mvae_ctx* ctx, const float* x, const mvae_pairs* pairs, float* zmean_out, void* stream) {
   hipStream_t st = (hipStream_t)stream;
-  int rc = encode(ctx, x, nullptr, st, ENC_MEAN);
+  int rc = encode(ctx, x, nullptr, st, ENC_MEAN, pairs);
   if (rc) return rc;
   MV_CHECK(launch_copy2d(ctx->ms + (size_t)ctx->B * 2 * ctx->L, 2 * ctx->L, zmean_out, ctx->L,
                          ctx->B, ctx->L, st));
@@ -1883,10 +1963,21 @@ extern "C" int mvae_transform(mvae_ctx* ctx, const float* x, float* zmean_out, v
   return MVAE_OK;
 }
 
-extern "C" int mvae_reconstruct(mvae_ctx* ctx, const float* x, const float* eps, float* y_out, void* stream) {
-  if (!ctx || !x || !y_out) return MVAE_EINVAL;
+extern "C" int mvae_transform(mvae_ctx* ctx, const float* x, float* zmean_out, void* stream) {
+  if (!ctx || !x || !zmean_out) return MVAE_EINVAL;
+  return transform_any(ctx, x, nullptr, zmean_out, stream);
+}
+
+extern "C" int mvae_transform_pairs(mvae_ctx* ctx, const mvae_pairs* pairs, float* zmean_out, void* stream) {
+  if (!ctx || !zmean_out) return MVAE_EINVAL;
+  if (int rc = check_pairs(ctx, pairs, "mvae_transform_pairs")) return rc;
+  return transform_any(ctx, nullptr, pairs, zmean_out, stream);
+}
+
+static int reconstruct_any(mvae_ctx* ctx, const float* x, const mvae_pairs* pairs, const float* eps, float* y_out,
+                           void* stream) {
   hipStream_t st = (hipStream_t)stream;
-  int rc = encode(ctx, x, eps, st, ENC_EVAL);
+  int rc = encode(ctx, x, eps, st, ENC_EVAL, pairs);
   if (rc) return rc;
   if ((rc = decode_hidden(ctx, st))) return rc;
   GemmDesc d = ctx->f_out;
@@ -1895,6 +1986,18 @@ extern "C" int mvae_reconstruct(mvae_ctx* ctx, const float* x, const float* eps,
   if ((rc = run(ctx, d, st))) return rc;
   ctx->phase = 0;
   return MVAE_OK;
+}
+
+extern "C" int mvae_reconstruct(mvae_ctx* ctx, const float* x, const float* eps, float* y_out, void* stream) {
+  if (!ctx || !x || !y_out) return MVAE_EINVAL;
+  return reconstruct_any(ctx, x, nullptr, eps, y_out, stream);
+}
+
+extern "C" int mvae_reconstruct_pairs(mvae_ctx* ctx, const mvae_pairs* pairs, const float* eps, float* y_out,
+                                      void* stream) {
+  if (!ctx || !y_out) return MVAE_EINVAL;
+  if (int rc = check_pairs(ctx, pairs, "mvae_reconstruct_pairs")) return rc;
+  return reconstruct_any(ctx, nullptr, pairs, eps, y_out, stream);
 }
 
 extern "C" int mvae_generate(mvae_ctx* ctx, const float* zin, int n, float* y_out, void* stream) {
@@ -2444,6 +2547,40 @@ extern "C" int mvae_debug_conv2(int S1, int B, int mode, int mfma, const float* 
   }
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   for (void* p : tmp) (void)hipFree(p);
+  if (e != hipSuccess) { g_create_err = hipGetErrorString(e); return (int)e; }
+  return MVAE_OK;
+}
+
+// The batch's bit operands on caller buffers (tests only; synchronous; allocates nothing): mode 0
+// launch_make_batch into x then launch_deint_bits (no_xbw: its variant 7), mode 1
+// launch_pairs_bits. S x S images, B rows. Caller buffers, zero-filled (padding is never written):
+// xbf bitmat_words(3B, D + 1) words, xbw bitmat_words(D + 1, 3B) words, xbits [B][ldbits] bytes,
+// dyn 4 ints, plane [3B][ldx] bf16 (plane 0, written when the not-binary word rises), x [B][3D]
+// floats (mode 0 only).
+extern "C" int mvae_debug_pairs_bits(const unsigned char* locks, const unsigned char* keys, const int* idx,
+                                     const float* coef, int B, int S, float divisor, int mode, int no_xbw,
+                                     float* x, unsigned* xbf, unsigned* xbw, unsigned char* xbits, int ldbits,
+                                     int* dyn, unsigned short* plane, int ldx, void* stream) {
+  if (!locks || !keys || !idx || !coef || B <= 0 || S <= 0 || S > 4096 || !(divisor > 0.f) || mode < 0 || mode > 1 ||
+      (mode == 0 && !x) || !xbf || !xbw || !xbits || !dyn || !plane || ldx < S * S || ldbits < (S * S + 7) / 8)
+    return fail(nullptr, MVAE_EINVAL, "mvae_debug_pairs_bits: bad argument");
+  hipStream_t st = (hipStream_t)stream;
+  const int D = S * S;
+  const Planes pl{plane, (long long)3 * B * ldx, 1};
+  const int kts_f = bitmat_kts(D + 1), kts_w = bitmat_kts(3 * B);
+  hipError_t e;
+  if (mode == 0) {
+    e = launch_make_batch(locks, keys, S, S, idx, coef, B, divisor, x, st);
+    if (e == hipSuccess)
+      e = launch_deint_bits(x, B, D, xbf, kts_f, xbw, kts_w, xbits, ldbits, dyn, dyn + 1, nullptr, pl, ldx, 0, st,
+                            no_xbw ? 7 : 0);
+  } else {
+    e = launch_pairs_bits(locks, keys, S, S, idx, coef, divisor, B, xbf, kts_f, xbw, kts_w, xbits, ldbits, dyn,
+                          dyn + 1, nullptr, pl, ldx, 0, no_xbw != 0, st);
+  }
+  if (e == hipErrorInvalidValue)
+    return fail(nullptr, MVAE_EINVAL, "mvae_debug_pairs_bits: shape or alignment the kernels do not serve");
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
   if (e != hipSuccess) { g_create_err = hipGetErrorString(e); return (int)e; }
   return MVAE_OK;
 }

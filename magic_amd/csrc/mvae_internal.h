@@ -285,6 +285,17 @@ hipError_t launch_binarize(float* x, size_t n, hipStream_t st);
 hipError_t launch_make_batch(const unsigned char* locks, const unsigned char* keys, int H, int W,
                              const int* idx, const float* coef, int B, float div, float* x,
                              hipStream_t st);
+// ---- a batch's bit operands straight from the uint8 tables (pairs_bits.hip) ----
+// What launch_make_batch followed by launch_deint_bits writes (the same bits: BitMats, target
+// bits, flag slots, and for a batch with a pixel other than 0 / 1 the planes, fp32 rows and inexact
+// flag of the grey pass), without X. no_xbw: the forward words only (launch_deint_bits variant 7).
+// Serves D = H W % 8 == 0, B % 64 == 0, 8-byte aligned tables and a 16-byte aligned coef
+// (pairs_bits_fits); hipErrorInvalidValue otherwise, before anything is launched.
+bool pairs_bits_fits(const unsigned char* locks, const unsigned char* keys, const float* coef, int B, int D);
+hipError_t launch_pairs_bits(const unsigned char* locks, const unsigned char* keys, int H, int W, const int* idx,
+                             const float* coef, float div, int B, unsigned* xbf, int kts_f, unsigned* xbw,
+                             int kts_w, unsigned char* xbits, int ldbits, int* dyn, int* dyn_next, float* xs,
+                             const Planes& xp, int ldx, int f32dyn_mask, bool no_xbw, hipStream_t st);
 // ---- conv-encoder tower (conv_tower.hip, conv_mfma.hip) ----
 // NHWC fp32 activations of the stacked batch (3B forward rows, 4B backward rows); S = image
 // side, S1 = S/2 (after pool 1), S2 = S/4 (after pool 2).

@@ -37,16 +37,7 @@ __device__ __forceinline__ int eps_slot(int blk) { return blk == 0 ? 1 : (blk ==
 // x[b][p*3 + c] (c: 0 lock, 1 rotated lock, 2 key; 11a/overlap_input.py:117-119,201)
 //  -> xs[(blk*B + b)][p], blk = {rot:0, lock:1, key:2}. Each thread moves 4 pixels:
 // three 16-B loads, three 16-B stores (coalesced both ways).
-// bf16 bits of v rounded to nearest even, and the exact remainder v - bf16(v)
-__device__ __forceinline__ unsigned short bf16_rn(float v, float& rem) {
-  const unsigned short b = __builtin_bit_cast(unsigned short, __float2bfloat16(v));
-  rem = v - __uint_as_float((unsigned)b << 16);
-  return b;
-}
-__device__ __forceinline__ uint2 pack4(unsigned short a, unsigned short b, unsigned short c,
-                                       unsigned short d) {
-  return make_uint2((unsigned)a | (unsigned)b << 16, (unsigned)c | (unsigned)d << 16);
-}
+// (bf16_rn, pack4: deint_bits.h)
 
 // [B, D, 3] interleaved (lock, rotated, key) -> row blocks [rot | lock | key] of the layer-0
 // operand: fp32 rows for the blocks in f32mask (bit c: block c; plane modes keep only the lock
@@ -88,49 +79,6 @@ __global__ void deinterleave_vec_kernel(const float4* __restrict__ x, float* __r
     }
   }
   if (dyn && __ballot(nz) != 0 && (threadIdx.x & 63) == 0) atomicOr(dyn, 1);
-}
-
-// 4 NQ pixels (3 NQ float4 of x in v, pixel order) of row b from column col -> the fp32 rows
-// of the blocks in f32mask and bf16 plane 0 (16-B stores); returns whether a pixel is inexact
-template <int NQ>
-__device__ __forceinline__ bool deint_put(const float4* v, float* __restrict__ xs,
-                                          unsigned short* __restrict__ xp, int B, int b,
-                                          size_t col, int ldx, int f32mask) {
-  static_assert(NQ % 2 == 0, "whole 16-B plane stores");
-  constexpr int NP = 4 * NQ;
-  bool nz = false;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    const int ch = c == 0 ? 1 : (c == 1 ? 0 : 2);  // block c (rot, lock, key) <- channel ch
-    float f[NP];
-#pragma unroll
-    for (int h = 0; h < NQ; ++h) {
-      const float4 a = v[3 * h], bb = v[3 * h + 1], cc = v[3 * h + 2];
-      const float e[12] = {a.x, a.y, a.z, a.w, bb.x, bb.y, bb.z, bb.w, cc.x, cc.y, cc.z, cc.w};
-#pragma unroll
-      for (int j = 0; j < 4; ++j) f[4 * h + j] = e[3 * j + ch];
-    }
-    const size_t o = (size_t)(c * B + b) * ldx + col;
-    if (f32mask >> c & 1) {
-#pragma unroll
-      for (int h = 0; h < NQ; ++h)
-        *reinterpret_cast<float4*>(xs + o + 4 * h) = make_float4(f[4 * h], f[4 * h + 1], f[4 * h + 2], f[4 * h + 3]);
-    }
-    if (xp) {
-#pragma unroll
-      for (int h = 0; h < NQ; h += 2) {
-        float r[8];
-        unsigned short h16[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) h16[j] = bf16_rn(f[4 * h + j], r[j]);
-        const uint2 lo = pack4(h16[0], h16[1], h16[2], h16[3]), hi = pack4(h16[4], h16[5], h16[6], h16[7]);
-        *reinterpret_cast<uint4*>(xp + o + 4 * h) = make_uint4(lo.x, lo.y, hi.x, hi.y);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) nz |= r[j] != 0.f;
-      }
-    }
-  }
-  return nz;
 }
 
 // The same for 4 NQ pixels per thread (D % (4 NQ) == 0): 3 NQ 16-B loads (48 NQ contiguous
@@ -976,24 +924,7 @@ __global__ void deint_grey_kernel(const float4* __restrict__ x, float* __restric
     float4 v[6];
 #pragma unroll
     for (int k = 0; k < 6; ++k) v[k] = src[k];
-    nz |= deint_put<2>(v, xs, xp, B, b, (size_t)8 * q, ldx, f32mask);
-    if (np == 3) {  // the exact split's residual planes of the 24 values
-      const float e[24] = {v[0].x, v[0].y, v[0].z, v[0].w, v[1].x, v[1].y, v[1].z, v[1].w,
-                           v[2].x, v[2].y, v[2].z, v[2].w, v[3].x, v[3].y, v[3].z, v[3].w,
-                           v[4].x, v[4].y, v[4].z, v[4].w, v[5].x, v[5].y, v[5].z, v[5].w};
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        const int ch = c == 0 ? 1 : (c == 1 ? 0 : 2);
-        const size_t o = (size_t)(c * B + b) * ldx + (size_t)8 * q;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          float r1, r2, r3;
-          (void)bf16_rn(e[3 * j + ch], r1);
-          xp[ps + o + j] = bf16_rn(r1, r2);
-          xp[2 * ps + o + j] = bf16_rn(r2, r3);
-        }
-      }
-    }
+    nz |= deint_grey_octet(v, xs, xp, ps, np, f32mask, B, b, q, ldx);
   }
   if (__ballot(nz) != 0 && (threadIdx.x & 63) == 0) atomicOr(dyn, 1);
 }

@@ -13,6 +13,7 @@ import torch
 
 from . import _lib
 from .config import MVAEConfig
+from .overlap_input import PairBatch
 
 PARAM_ORDER_DEAD = ("dec_out_log_sigma_W", "dec_out_log_sigma_b")
 
@@ -26,7 +27,8 @@ def _ptr(t: Optional[torch.Tensor]):
 
 
 class Engine:
-    """Owns an ``mvae_ctx``. Tensors passed in must be contiguous float32 on ``device``."""
+    """Owns an ``mvae_ctx``. Tensors passed in must be contiguous float32 on ``device``; wherever
+    a method takes the batch ``x`` it also takes an ``overlap_input.PairBatch``."""
 
     def __init__(self, cfg: MVAEConfig, device: int = 0):
         if not torch.cuda.is_available():
@@ -177,14 +179,40 @@ class Engine:
 
     # ------------------------------------------------------------------ step phases
     def _xin(self, x):
-        if x.shape != (self.cfg.batch, 3 * self.cfg.D):
+        if tuple(x.shape) != (self.cfg.batch, 3 * self.cfg.D):
             raise ValueError(f"X must be [{self.cfg.batch}, {3 * self.cfg.D}] (got {tuple(x.shape)})")
+        if isinstance(x, PairBatch):
+            return self._pairs(x)
         return _ptr(x)
 
-    def forward(self, x: torch.Tensor, eps: Optional[torch.Tensor] = None):
+    def _pairs(self, pb: PairBatch):
+        """The ``mvae_pairs`` descriptor of a ``PairBatch`` (tensors re-checked: they are mutable
+        attributes). Square tables only, as ``cfg.image_size``."""
+        for t, dt in ((pb.locks, torch.uint8), (pb.keys, torch.uint8), (pb.idx, torch.int32),
+                      (pb.coef, torch.float32)):
+            if not t.is_cuda or t.dtype != dt or not t.is_contiguous():
+                raise ValueError("PairBatch: contiguous device tensors (uint8 tables, int32 idx, float32 coef) "
+                                 "expected")
+        if pb.keys.shape != pb.locks.shape or tuple(pb.coef.shape) != (self.cfg.batch, 4):
+            raise ValueError("PairBatch: lock / key tables of one shape and coef [B, 4] expected")
+        p = _lib.mvae_pairs()
+        p.locks, p.keys = pb.locks.data_ptr(), pb.keys.data_ptr()
+        p.height, p.width = int(pb.locks.shape[1]), int(pb.locks.shape[2])
+        p.idx, p.coef = pb.idx.data_ptr(), pb.coef.data_ptr()
+        p.divisor = 255.0 if pb.normalize else 1.0
+        return p
+
+    def _call(self, name: str, x, *args):
+        """``mvae_<name>`` on an X tensor, ``mvae_<name>_pairs`` on a ``PairBatch``."""
+        xin = self._xin(x)
+        if isinstance(xin, _lib.mvae_pairs):
+            return self._check(getattr(self.lib, f"mvae_{name}_pairs")(self.ctx, C.byref(xin), *args))
+        return self._check(getattr(self.lib, f"mvae_{name}")(self.ctx, xin, *args))
+
+    def forward(self, x, eps: Optional[torch.Tensor] = None):
         if eps is not None and eps.shape != (3, self.cfg.batch, self.cfg.latent):
             raise ValueError("eps must be [3, B, L] (lock, rotated lock, key)")
-        self._check(self.lib.mvae_forward(self.ctx, self._xin(x), _ptr(eps), self.stream))
+        self._call("forward", x, _ptr(eps), self.stream)
 
     def metric(self, areas: torch.Tensor):
         if areas.shape != (self.cfg.batch,):
@@ -226,17 +254,16 @@ class Engine:
     def train_step(self, x, areas, eps=None, losses_out=None, dist_out=None):
         if areas.shape != (self.cfg.batch,):
             raise ValueError("overlap_areas must be [B]")
-        self._check(self.lib.mvae_train_step(self.ctx, self._xin(x), _ptr(areas), _ptr(eps),
-                                             _ptr(losses_out), _ptr(dist_out), self.stream))
+        self._call("train_step", x, _ptr(areas), _ptr(eps), _ptr(losses_out), _ptr(dist_out), self.stream)
 
     def predict(self, x, eps=None, out=None):
         out = out if out is not None else torch.empty(self.cfg.batch, device=self.dev)
-        self._check(self.lib.mvae_predict(self.ctx, self._xin(x), _ptr(eps), _ptr(out), self.stream))
+        self._call("predict", x, _ptr(eps), _ptr(out), self.stream)
         return out
 
     def predict_encode(self, x, eps=None):
         """First phase of ``predict``: encoder + (cosine) the local column sums ``colsq``."""
-        self._check(self.lib.mvae_predict_encode(self.ctx, self._xin(x), _ptr(eps), self.stream))
+        self._call("predict_encode", x, _ptr(eps), self.stream)
 
     def predict_finish(self, out=None):
         """Second phase: distances with the current ``colsq`` (all-reduced under DP)."""
@@ -246,12 +273,12 @@ class Engine:
 
     def transform(self, x, out=None):
         out = out if out is not None else torch.empty(self.cfg.batch, self.cfg.latent, device=self.dev)
-        self._check(self.lib.mvae_transform(self.ctx, self._xin(x), _ptr(out), self.stream))
+        self._call("transform", x, _ptr(out), self.stream)
         return out
 
     def reconstruct(self, x, eps=None, out=None):
         out = out if out is not None else torch.empty(self.cfg.batch, self.cfg.D, device=self.dev)
-        self._check(self.lib.mvae_reconstruct(self.ctx, self._xin(x), _ptr(eps), _ptr(out), self.stream))
+        self._call("reconstruct", x, _ptr(eps), _ptr(out), self.stream)
         return out
 
     def generate(self, z: torch.Tensor, out=None):

@@ -110,13 +110,16 @@ def main(argv=None):
     ap.add_argument("--samples-per-epoch", type=int, default=FLAGS.NUM_EXAMPLES_PER_EPOCH_FOR_TRAIN)
     ap.add_argument("--driver", choices=sorted(DRIVERS), default=None,
                     help="reference driver semantics (default: 8c for the 8c-family presets)")
+    ap.add_argument("--fused-input", action="store_true",
+                    help="feed the step PairBatch descriptions of the batches (inputs(fused=True)): the "
+                         "same batches and results without the float32 X array")
     args = ap.parse_args(argv)
     cfg = preset(args.preset, image_size=args.image_size, batch=args.batch or None)
     eight_c = args.preset in ("8c", "8d", "8e", "8f")
     driver = args.driver or ("8c" if eight_c else "11a")
     vae = TangoEncoder(None, config=cfg, compat="8c" if eight_c else "11a")
     batches = overlap_input.inputs(normalize=True, reshape=True, rotation=True, batch_size=cfg.batch,
-                                   image_size=cfg.image_size, data_dir=args.data)
+                                   image_size=cfg.image_size, data_dir=args.data, fused=args.fused_input)
     t0 = time.time()
     train(vae, batches, max(args.samples_per_epoch, cfg.batch), args.epochs, driver=driver)
     print(f"done in {time.time() - t0:.1f}s", file=sys.stderr)

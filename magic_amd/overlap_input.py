@@ -62,6 +62,36 @@ def make_batch(locks: torch.Tensor, keys: torch.Tensor, idx: torch.Tensor, coef:
     return out
 
 
+class PairBatch:
+    """One batch described by its sources instead of materialised: the uint8 device tables
+    ``locks`` / ``keys`` [n, H, W], the example ``idx`` int32 [B] of each row and its rotation
+    ``coef`` float32 [B, 4] (``rotation_coefficients``). ``Engine`` and ``TangoEncoder`` take it
+    wherever they take X (``mvae_*_pairs``): where the step writes its layer-0 bit operands, one
+    HIP kernel reads them straight from the tables, and no [B, H*W*3] float32 array exists.
+    ``materialize()`` is that array, ``make_batch(...)``: the results are bitwise the same."""
+
+    def __init__(self, locks: torch.Tensor, keys: torch.Tensor, idx: torch.Tensor, coef: torch.Tensor,
+                 normalize: bool = True):
+        for t, dt in ((locks, torch.uint8), (keys, torch.uint8), (idx, torch.int32), (coef, torch.float32)):
+            if not t.is_cuda or t.dtype != dt or not t.is_contiguous():
+                raise ValueError("PairBatch: device tensors (uint8 tables, int32 idx, float32 coef) expected")
+        if locks.dim() != 3 or keys.shape != locks.shape or idx.dim() != 1 or coef.shape != (idx.shape[0], 4):
+            raise ValueError("PairBatch: tables [n, H, W] of one shape, idx [B], coef [B, 4] expected")
+        self.locks, self.keys, self.idx, self.coef = locks, keys, idx, coef
+        self.normalize = bool(normalize)
+
+    @property
+    def shape(self):
+        return (self.idx.shape[0], 3 * self.locks.shape[1] * self.locks.shape[2])
+
+    @property
+    def device(self):
+        return self.locks.device
+
+    def materialize(self, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        return make_batch(self.locks, self.keys, self.idx, self.coef, out=out, normalize=self.normalize)
+
+
 def random_shapes(n: int, size: int, gen: torch.Generator, device) -> torch.Tensor:
     """Binary images {0,1} of 1-3 random filled ellipses/rectangles (foreground ~3-15%, like
     the reference's overlap_micro PNGs), [n, size, size] float32."""
@@ -169,11 +199,16 @@ class PairSource:
 class BatchStream:
     """Shuffled epochs over a source (``slice_input_producer(shuffle=True)`` +
     ``shuffle_batch``), a uniform [0, 2pi) rotation per example, /255 normalisation — the
-    per-batch assembly runs in the HIP batch producer (``mvae_make_batch``)."""
+    per-batch assembly runs in the HIP batch producer (``mvae_make_batch``). ``fused=True``: the
+    same draws yield ``(PairBatch, areas)`` and launch nothing; the step reads the tables."""
 
     def __init__(self, batch: int, image_size: int, source: Optional[PairSource] = None,
                  normalize: bool = True, seed: int = 1, device="cuda", synthetic_pool: int = 960,
-                 reshape: bool = True, fp16: bool = False):
+                 reshape: bool = True, fp16: bool = False, fused: bool = False):
+        if fused and (not reshape or fp16):
+            raise ValueError("fused=True yields a PairBatch, not an array: reshape=False and USE_FP16 "
+                             "ask for the array")
+        self.fused = fused
         self.batch, self.size = batch, image_size
         self.normalize, self.reshape, self.fp16 = normalize, reshape, fp16
         self.device = torch.device(device)
@@ -216,8 +251,10 @@ class BatchStream:
         ang = self.rng.uniform(0.0, 2 * math.pi, self.batch)
         coef = torch.from_numpy(rotation_coefficients(ang, self.size, self.size)).to(self.device)
         idx_t = torch.from_numpy(idx.astype(np.int32)).to(self.device)
-        x = make_batch(self.locks, self.keys, idx_t, coef, normalize=self.normalize)
         a = self.areas[idx_t.long()]
+        if self.fused:
+            return PairBatch(self.locks, self.keys, idx_t, coef, normalize=self.normalize), a
+        x = make_batch(self.locks, self.keys, idx_t, coef, normalize=self.normalize)
         if not self.reshape:  # [B, H, W, 3] (11a/overlap_input.py:117-119 not applied)
             x = x.view(self.batch, self.size, self.size, 3)
         if self.fp16:  # FLAGS.USE_FP16 casts images and labels (11a/overlap_input.py:109-111)
@@ -227,10 +264,13 @@ class BatchStream:
 
 def inputs(normalize: bool = False, reshape: bool = False, rotation: bool = False,
            batch_size: Optional[int] = None, image_size: Optional[int] = None,
-           data_dir: Optional[str] = None, device="cuda", seed: int = 1) -> BatchStream:
+           data_dir: Optional[str] = None, device="cuda", seed: int = 1,
+           fused: bool = False) -> BatchStream:
     """``11a/overlap_input.py:76-122``: images [B, H*W*3] (``reshape=True``) or [B, H, W, 3],
     divided by 255 when ``normalize``, cast to float16 with labels when ``FLAGS.USE_FP16``;
-    ``rotation=False`` raises as in the reference (``:95-96``)."""
+    ``rotation=False`` raises as in the reference (``:95-96``). ``fused=True`` (needs
+    ``reshape=True`` and no ``USE_FP16``): images are ``PairBatch`` descriptions of the same
+    batches, which ``TangoEncoder`` takes as X."""
     if not rotation:
         raise ValueError("Rotation has to be True.")
     size = image_size or FLAGS.IMAGE_SIZE
@@ -241,4 +281,4 @@ def inputs(normalize: bool = False, reshape: bool = False, rotation: bool = Fals
         lim = FLAGS.NUM_EXAMPLES_TO_LOAD_INTO_QUEUE
         src = PairSource.from_packed(d, limit=lim) if d.endswith(".npz") else PairSource(d, limit=lim)
     return BatchStream(bs, size, src, normalize=normalize, seed=seed, device=device, reshape=reshape,
-                       fp16=bool(getattr(FLAGS, "USE_FP16", False)))
+                       fp16=bool(getattr(FLAGS, "USE_FP16", False)), fused=fused)

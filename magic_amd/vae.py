@@ -16,7 +16,9 @@ methods and return values:
 X is ``[B, H*W*3]`` float32, HWC-interleaved (lock, rotated lock, key) exactly as
 ``overlap_input.inputs(normalize=True, reshape=True, rotation=True)`` yields it. Inputs may
 be numpy arrays (copied host->device, as ``feed_dict`` did) or float32 device tensors
-(no copy). Outputs are numpy arrays like ``sess.run`` results.
+(no copy), or an ``overlap_input.PairBatch`` as ``inputs(..., fused=True)`` yields it (the batch
+described by its uint8 tables; same results, no X array). Outputs are numpy arrays like
+``sess.run`` results.
 """
 from __future__ import annotations
 
@@ -28,6 +30,7 @@ import torch
 from .config import MVAEConfig, preset
 from .constants import FLAGS, metric_name
 from .engine import Engine
+from .overlap_input import PairBatch
 
 
 def _default_config() -> MVAEConfig:
@@ -83,6 +86,8 @@ class TangoEncoder(object):
         return t
 
     def _x(self, X):
+        if isinstance(X, PairBatch):  # a batch described by its sources: the engine reads the tables
+            return X
         return self._dev(X, (self.batch_size, self.num_input_neurons))
 
     # ----------------------------------------------------------------- reference API

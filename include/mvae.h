@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define MVAE_ABI_VERSION 5
+#define MVAE_ABI_VERSION 6
 #define MVAE_MAX_ENC 8
 
 enum { MVAE_OK = 0, MVAE_EINVAL = -1, MVAE_ECONFIG = -2, MVAE_ESTATE = -3 };
@@ -281,6 +281,58 @@ int mvae_transform_pairs(mvae_ctx* ctx, const mvae_pairs* pairs, float* zmean_ou
 int mvae_reconstruct_pairs(mvae_ctx* ctx, const mvae_pairs* pairs, const float* eps, float* y_out,
                            void* stream);
 
+/* ---- retrieval: embed a gallery, score every lock against every key ------------------ */
+/* Any number of single images from one uint8 table, encoded to their latent mean (and log-sigma):
+ * what a trained metric model is used for. The call runs ceil(count / 3B) encoder passes; image t
+ * of a pass (0 <= t < 3B) is row t of the context's stacked layer-0 operand, so every row of the
+ * 3B-row encoder GEMMs carries a wanted image (mvae_transform carries one in three) and the rows
+ * of the block mvae_transform copies from, [B, 2B), are bitwise what mvae_transform_pairs returns
+ * for the same images as locks. Rows of the last pass at or past count are all-zero images: idx is
+ * not read for them and nothing is written to the outputs past row count - 1.
+ *
+ * Direct path: exactly where the *_pairs twins take theirs (bf16 / f32x precision with the default
+ * "bits" and "e8" plans, FC encoder, batch % 64 == 0, image_size^2 % 8 == 0, no deint_fuse and no
+ * diag_* option) and the table is 8-byte aligned, one kernel writes the layer-0 bit operand from
+ * the table with three 8-byte loads per pixel octet (timing region "images_bits"). Every other
+ * configuration materialises the pass as X -- x[b, 3 p + ch] = image((1, 0, 2)[ch] B + b)[p] /
+ * divisor, the channel of stacked block 0, 1, 2 being the rotated lock's, the lock's, the key's --
+ * into the context's lazily allocated [B, 3 D] scratch and runs the x code. Both routes give the
+ * same bits where both exist.
+ *
+ * No eps is drawn and no RNG counter moves; the call leaves the context idle (as mvae_transform)
+ * and may stand between two training steps without changing them. Preconditions as for
+ * mvae_make_batch: every idx[i] in [0, n) (not checked: the kernels index the table with it); the
+ * table and idx are read by the kernels the call enqueues. A null descriptor, table or zmean_out,
+ * count < 1, a height / width other than cfg.image_size or a divisor <= 0 is MVAE_EINVAL with a
+ * message. */
+typedef struct mvae_images {
+  const unsigned char* table;  /* device uint8 [n][H][W]                                        */
+  int height, width;           /* must equal cfg.image_size                                     */
+  const int* idx;              /* device int32 [count], each in [0, n); NULL: images 0..count-1 */
+  float divisor;               /* 255 or 1, as mvae_pairs                                       */
+} mvae_images;
+/* zmean_out [count, L]; zlogsig_out [count, L] or NULL. */
+int mvae_embed_images(mvae_ctx* ctx, const mvae_images* images, int64_t count, float* zmean_out,
+                      float* zlogsig_out, void* stream);
+/* zl [N, L], zk [M, L] fp32 device, row stride L. score(i, j) = the context's distance (cfg.metric,
+ * cfg.reciprocal; 11a/vae.py:306-311, 444-458 taken to all pairs) between lock embedding i and key
+ * embedding j: sqdiff raw = sum_l (zl[i,l] - zk[j,l])^2, summed in fp32 in that difference form;
+ * cosine raw = sum_l (zl[i,l] rl[l]) (zk[j,l] rk[l]) with rl[l] = rsqrt(max(sum_i zl[i,l]^2, 1e-12))
+ * over the N lock rows and rk the same over the M key rows (the galleries are the batch the
+ * axis-0 l2_normalize ranges over; the column sums are taken in a fixed order; a NaN column sum is
+ * clamped by the max to 1e-12 like a zero one, as in the step's metric kernel, so a NaN embedding
+ * row leaves the norms numbers and makes only its own scores NaN); reciprocal: 1 / raw.
+ * top_val / top_idx [N, k], 1 <= k <= min(M, 64): the k best keys of each lock in a total order --
+ * by score (order +1: largest first, -1: smallest first), then by smaller j; NaN last for either
+ * order. dist_out: NULL, or [N, M] to also store every score; top_val[i, r] is bit for bit
+ * dist_out[i, top_idx[i, r]], and top_val / top_idx do not depend on whether dist_out is given nor
+ * on how the call splits M over workgroups. With dist_out NULL no N x M buffer exists: the
+ * workspace, O(N k splits) (+ O((N + M) L / 256) for the cosine norms), is allocated at the first
+ * call that needs it and reused (growing it waits for the whole device first: an earlier call on
+ * any stream may still read the old one). N, M >= 1, M < 2^31; else MVAE_EINVAL with a message. */
+int mvae_match(mvae_ctx* ctx, const float* zl, int64_t N, const float* zk, int64_t M, int k, int order,
+               float* dist_out, float* top_val, int* top_idx, void* stream);
+
 /* ---- diagnostics ------------------------------------------------------------------ */
 /* HIP-event timing of named regions (one GEMM incl. its split-K reduction, or one
  * bandwidth kernel group), recorded on the launch stream while enabled.               */
@@ -317,7 +369,10 @@ int mvae_debug_conv2(int S1, int B, int mode, int mfma, const float* x, const fl
                      void* stream);
 /* The bit operands of a batch of S x S images on caller buffers (tests; synchronous; allocates
  * nothing). mode 0: mvae_make_batch into x [B][3 S S], then the step's de-interleave to bits;
- * mode 1: the direct kernel of the *_pairs entry points. no_xbw: the forward words only (the
+ * mode 1: the direct kernel of the *_pairs entry points; mode 2: the direct kernel of
+ * mvae_embed_images -- locks is the one table, idx holds 3B entries (the images of stacked rows
+ * 0 .. 3B - 1), keys and coef are not read; mode 3: the step's de-interleave alone on the caller's
+ * x (mode 2's reference). no_xbw: the forward words only (the
  * xbw_split schedule). Outputs, zero-filled by the caller (padding is never written): xbf
  * ceil(3B/256) ceil((D+1)/64) 512 words, xbw ceil((D+1)/256) ceil(3B/64) 512 words, xbits
  * [B][ldbits] bytes, dyn 4 ints (slot 0: words 0 inexact, 2 not-binary), and -- written only when

@@ -14,7 +14,7 @@ LIB_PATH = os.environ.get("MVAE_LIB", os.path.join(HERE, "libmvae.so"))
 
 MVAE_MAX_ENC = 8
 MARKER_GRID = 4096   # mvae_region_marker workgroups = MARKER_GRID + region (mvae_internal.h)
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 ACT = {"tanh": 0, "elu": 1}
 METRIC = {"cosine": 0, "sqdiff": 1}
@@ -50,6 +50,12 @@ class mvae_pairs(C.Structure):
     """A batch described by its sources (``include/mvae.h``): device pointers and sizes."""
     _fields_ = [("locks", C.c_void_p), ("keys", C.c_void_p), ("height", C.c_int), ("width", C.c_int),
                 ("idx", C.c_void_p), ("coef", C.c_void_p), ("divisor", C.c_float)]
+
+
+class mvae_images(C.Structure):
+    """Single images of one uint8 table (``include/mvae.h``): device pointers and sizes."""
+    _fields_ = [("table", C.c_void_p), ("height", C.c_int), ("width", C.c_int), ("idx", C.c_void_p),
+                ("divisor", C.c_float)]
 
 
 class mvae_tensor(C.Structure):
@@ -99,6 +105,10 @@ _SIGS = {
     "mvae_transform_pairs": ([C.c_void_p, C.POINTER(mvae_pairs), C.c_void_p, C.c_void_p], C.c_int),
     "mvae_reconstruct_pairs": ([C.c_void_p, C.POINTER(mvae_pairs), C.c_void_p, C.c_void_p, C.c_void_p],
                                C.c_int),
+    "mvae_embed_images": ([C.c_void_p, C.POINTER(mvae_images), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
+                          C.c_int),
+    "mvae_match": ([C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p,
+                    C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
     "mvae_timing_enable": ([C.c_void_p, C.c_int], C.c_int),
     "mvae_timing_select": ([C.c_void_p, C.c_int], C.c_int),
     "mvae_timing_marker": ([C.c_void_p, C.c_int, C.c_int], C.c_int),

@@ -195,6 +195,21 @@ __device__ __forceinline__ bool deint_octet(const float (&e)[24], unsigned (&by3
   return nb;
 }
 
+// An octet's 24 values as X would store them, from the raw bytes of its 8 pixels in the three
+// channels (eight bytes per uint2, pixel j in byte j): per pixel (lock, rotated lock, key) / div,
+// the producer's (float)byte / div. Shared by the kernels that read the uint8 tables
+// (pairs_bits.hip, images_bits.hip).
+__device__ __forceinline__ void deint_byte_values(const uint2& l, const uint2& r, const uint2& k, float div,
+                                                  float (&e)[24]) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int sh = 8 * (j & 3);
+    e[3 * j] = (float)(((j < 4 ? l.x : l.y) >> sh) & 0xFFu) / div;
+    e[3 * j + 1] = (float)(((j < 4 ? r.x : r.y) >> sh) & 0xFFu) / div;
+    e[3 * j + 2] = (float)(((j < 4 ? k.x : k.y) >> sh) & 0xFFu) / div;
+  }
+}
+
 // the task's BitMat words from its LDS bytes, by threads t0, t0 + nt, ...: the forward words four
 // at a time (lanes 2 q, 2 q + 1 of the fragment layout, words j = 0 / 1 each: rows 16 (2 j + h) +
 // (lane & 15), k-octet 8 kk + 4 kh + (lane >> 4); one 16-B store, SC1 written through), the

@@ -52,6 +52,11 @@ struct mvae_ctx {
   // a batch given as (tables, idx, coefficients) (the *_pairs entry points) where the direct
   // kernel does not apply: X materialised here (launch_make_batch), allocated on first need
   float* pairs_x = nullptr;
+  // mvae_match's workspace, allocated at the first call that needs it and grown on demand: the
+  // per-split top-k lists [N][splits][k] (values, indices) and, for the cosine metric, the column
+  // norms' chunk sums and reciprocal norms of both galleries
+  void* match_ws = nullptr;
+  size_t match_ws_bytes = 0;
   int B = 0, D = 0, L = 0, nenc = 0, d0 = 0, d1 = 0;
   float inv_bg = 1.f;
   int ldx = 0, ldz = 0, ld_d1 = 0, ld_d2 = 0, ld_u = 0, lddz = 0, ld_dh = 0, nblk = 0, nchunk = 0;
@@ -447,6 +452,7 @@ int mvae_destroy(mvae_ctx* ctx) {
   if (ctx->side) hipStreamDestroy(ctx->side);
   if (ctx->stage) hipStreamDestroy(ctx->stage);
   for (void* p : ctx->allocs) hipFree(p);
+  if (ctx->match_ws) hipFree(ctx->match_ws);
   hipSetDevice(dev);
   delete ctx;
   return MVAE_OK;
@@ -1331,11 +1337,22 @@ static int shadow_deint(mvae_ctx* ctx, hipStream_t st);
 // (launch_pairs_bits: the BitMats straight from the tables) exactly where an x batch would take the
 // plain bits branch below and the launcher's shape / alignment conditions hold; in every other
 // configuration X is materialised into the context's scratch and the x code runs on it.
+//
+// One pass of mvae_embed_images (x and pairs NULL): the 3B images [first, first + 3B) of the call,
+// image t of the pass being stacked row t; it takes its direct kernel (launch_images_bits) under
+// the same conditions, else launch_images_x materialises the pass into the same scratch.
+struct EmbedPass {
+  const mvae_images* im;
+  const int* idx;  // im->idx + first, or NULL
+  const unsigned char* table;  // im->table (idx given) or im->table + first D
+  int nvalid;      // min(3B, count - first)
+};
 static int encode(mvae_ctx* ctx, const float* x, const float* eps, hipStream_t st, int draw = ENC_TRAIN,
-                  const mvae_pairs* pairs = nullptr) {
+                  const mvae_pairs* pairs = nullptr, const EmbedPass* ep = nullptr) {
   auto c = ctx;
-  const bool direct = pairs && c->bits_on && !c->fuse && !c->diag_skip_deint && !c->diag_shadow &&
-                      pairs_bits_fits(pairs->locks, pairs->keys, pairs->coef, c->B, c->D);
+  const bool bits_plain = c->bits_on && !c->fuse && !c->diag_skip_deint && !c->diag_shadow;
+  const bool direct = bits_plain && ((pairs && pairs_bits_fits(pairs->locks, pairs->keys, pairs->coef, c->B, c->D)) ||
+                                     (ep && images_bits_fits(ep->table, c->B, c->D)));
   if (c->side && c->side_pending) {  // an early-Adam backward whose mvae_adam never came
     c->side_pending = false;
     c->early_fork = false;
@@ -1351,16 +1368,22 @@ static int encode(mvae_ctx* ctx, const float* x, const float* eps, hipStream_t s
     MV_CHECK(hipEventRecord(c->sync_ev[c->sync_next % c->sync_ev.size()], c->stage));
     MV_CHECK(hipStreamWaitEvent(st, c->sync_ev[c->sync_next++ % c->sync_ev.size()], 0));
   }
-  if (pairs && !direct) {
+  if ((pairs || ep) && !direct) {
     if (!c->pairs_x) {
       void* q = nullptr;
       MV_CHECK(hipMalloc(&q, (size_t)c->B * 3 * c->D * sizeof(float)));
       c->allocs.push_back(q);
       c->pairs_x = static_cast<float*>(q);
     }
-    TIMED("pairs_make_batch");
-    MV_CHECK(launch_make_batch(pairs->locks, pairs->keys, pairs->height, pairs->width, pairs->idx, pairs->coef,
-                               c->B, pairs->divisor, c->pairs_x, st));
+    if (pairs) {
+      TIMED("pairs_make_batch");
+      MV_CHECK(launch_make_batch(pairs->locks, pairs->keys, pairs->height, pairs->width, pairs->idx, pairs->coef,
+                                 c->B, pairs->divisor, c->pairs_x, st));
+    } else {
+      TIMED("images_make_x");
+      MV_CHECK(launch_images_x(ep->table, ep->im->height, ep->im->width, ep->idx, ep->nvalid, ep->im->divisor, c->B,
+                               c->pairs_x, st));
+    }
     x = c->pairs_x;
   }
   c->last_x = x;
@@ -1393,14 +1416,18 @@ static int encode(mvae_ctx* ctx, const float* x, const float* eps, hipStream_t s
     c->dyn_cur = cur;
     f0_done = true;
   } else if (!(c->diag_skip_deint && c->dyn_cur)) {  // (diagnostics: the stale image of the last pass)
-    TimeScope ts_deint(ctx, region(ctx, direct ? "pairs_bits" : "deinterleave"), st);
+    TimeScope ts_deint(ctx, region(ctx, direct ? (ep ? "images_bits" : "pairs_bits") : "deinterleave"), st);
     // the flag's slots alternate: this pass raises the one the previous pass zeroed and zeroes
     // the previous one (its readers are all behind on this stream), no memset launch per step
     int* prev = c->dyn_cur ? c->dyn_cur : c->dyn;
     int* cur = c->dyn ? (prev == c->dyn ? c->dyn + 1 : c->dyn) : nullptr;
     if (c->bits_on) {  // the BitMats and target bits; the planes only for a batch not all 0 / 1
       const bool split = c->xbw_split && draw == ENC_TRAIN;  // (eval passes need no xbw)
-      if (direct)
+      if (direct && ep)  // (an evaluation pass: the forward words only, no transpose)
+        MV_CHECK(launch_images_bits(ep->table, ep->im->height, ep->im->width, ep->idx, ep->nvalid, ep->im->divisor,
+                                    c->B, c->xbf, c->kts_f, c->xbw, c->kts_w, c->xbits, c->ldbits, cur, prev, c->xs,
+                                    planes_of(c, c->xs), c->ldx, c->x32dyn, true, st));
+      else if (direct)
         MV_CHECK(launch_pairs_bits(pairs->locks, pairs->keys, pairs->height, pairs->width, pairs->idx, pairs->coef,
                                    pairs->divisor, c->B, c->xbf, c->kts_f, c->xbw, c->kts_w, c->xbits, c->ldbits,
                                    cur, prev, c->xs, planes_of(c, c->xs), c->ldx, c->x32dyn, split, st));
@@ -1972,6 +1999,87 @@ extern "C" int mvae_transform_pairs(mvae_ctx* ctx, const mvae_pairs* pairs, floa
   if (!ctx || !zmean_out) return MVAE_EINVAL;
   if (int rc = check_pairs(ctx, pairs, "mvae_transform_pairs")) return rc;
   return transform_any(ctx, nullptr, pairs, zmean_out, stream);
+}
+
+// ceil(count / 3B) encoder passes, every stacked row a wanted image; the means (and log-sigmas) of
+// a pass's rows leave ms with one strided copy per output, clipped to count
+extern "C" int mvae_embed_images(mvae_ctx* ctx, const mvae_images* im, int64_t count, float* zmean_out,
+                                 float* zlogsig_out, void* stream) {
+  if (!ctx) return MVAE_EINVAL;
+  if (!im || !im->table || !zmean_out)
+    return fail(ctx, MVAE_EINVAL, "mvae_embed_images: null images descriptor, table or zmean_out");
+  if (count < 1) return fail(ctx, MVAE_EINVAL, "mvae_embed_images: count must be at least 1");
+  if (im->height != ctx->cfg.image_size || im->width != ctx->cfg.image_size)
+    return fail(ctx, MVAE_EINVAL, "mvae_embed_images: table is " + std::to_string(im->height) + " x " +
+                                      std::to_string(im->width) + ", the context's image_size is " +
+                                      std::to_string(ctx->cfg.image_size));
+  if (!(im->divisor > 0.f)) return fail(ctx, MVAE_EINVAL, "mvae_embed_images: divisor must be positive");
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t rows = 3 * (int64_t)ctx->B;
+  const int L = ctx->L;
+  for (int64_t first = 0; first < count; first += rows) {
+    EmbedPass ep;
+    ep.im = im;
+    ep.idx = im->idx ? im->idx + first : nullptr;
+    ep.table = im->idx ? im->table : im->table + (size_t)first * ctx->D;
+    ep.nvalid = (int)std::min<int64_t>(rows, count - first);
+    int rc = encode(ctx, nullptr, nullptr, st, ENC_MEAN, nullptr, &ep);
+    if (rc) return rc;
+    TIMED("embed_copy_out");
+    MV_CHECK(launch_copy2d(ctx->ms, 2 * L, zmean_out + (size_t)first * L, L, ep.nvalid, L, st));
+    if (zlogsig_out) MV_CHECK(launch_copy2d(ctx->ms + L, 2 * L, zlogsig_out + (size_t)first * L, L, ep.nvalid, L, st));
+  }
+  ctx->phase = 0;
+  return MVAE_OK;
+}
+
+extern "C" int mvae_match(mvae_ctx* ctx, const float* zl, int64_t N, const float* zk, int64_t M, int k, int order,
+                          float* dist_out, float* top_val, int* top_idx, void* stream) {
+  if (!ctx) return MVAE_EINVAL;
+  if (!zl || !zk || !top_val || !top_idx) return fail(ctx, MVAE_EINVAL, "mvae_match: null zl, zk, top_val or top_idx");
+  if (N < 1 || M < 1 || M > 0x7FFFFFFFll || N > (0x7FFFFFFFll << 6))
+    return fail(ctx, MVAE_EINVAL, "mvae_match: N and M must be at least 1 (M below 2^31)");
+  if (k < 1 || k > 64 || k > M) return fail(ctx, MVAE_EINVAL, "mvae_match: k must be in [1, min(M, 64)]");
+  if (order != 1 && order != -1) return fail(ctx, MVAE_EINVAL, "mvae_match: order must be +1 or -1");
+  hipStream_t st = (hipStream_t)stream;
+  const int L = ctx->L;
+  const bool cosine = ctx->cfg.metric == MVAE_METRIC_COSINE;
+  long long split_len = 0;
+  int splits = 1;
+  match_plan(N, M, &split_len, &splits);
+  // workspace: [per-split values | indices | chunk sums of zl, zk (doubles) | rl | rk]
+  const size_t n_list = splits > 1 ? (size_t)N * splits * k : 0;
+  const size_t pl = cosine ? (size_t)match_colnorm_chunks(N) * L : 0, pk = cosine ? (size_t)match_colnorm_chunks(M) * L : 0;
+  const size_t o_idx = align64(n_list * 4), o_part = o_idx + align64(n_list * 4);
+  const size_t o_r = o_part + align64((pl + pk) * 8), need = o_r + (cosine ? 2 * align64((size_t)L * 4) : 0);
+  if (need > ctx->match_ws_bytes) {
+    if (ctx->match_ws) {  // (its last readers may still be queued, on this stream or another)
+      MV_CHECK(hipDeviceSynchronize());
+      MV_CHECK(hipFree(ctx->match_ws));
+      ctx->match_ws = nullptr;
+      ctx->match_ws_bytes = 0;
+    }
+    MV_CHECK(hipMalloc(&ctx->match_ws, need));
+    ctx->match_ws_bytes = need;
+  }
+  // (sqdiff in one split needs no workspace at all: ws may then be null and is not offset)
+  char* ws = static_cast<char*>(ctx->match_ws);
+  float* ws_val = n_list ? reinterpret_cast<float*>(ws) : nullptr;
+  int* ws_idx = n_list ? reinterpret_cast<int*>(ws + o_idx) : nullptr;
+  float* rl = nullptr;
+  float* rk = nullptr;
+  if (cosine) {
+    TIMED("match_colnorm");
+    double* part = reinterpret_cast<double*>(ws + o_part);
+    rl = reinterpret_cast<float*>(ws + o_r);
+    rk = reinterpret_cast<float*>(ws + o_r + align64((size_t)L * 4));
+    MV_CHECK(launch_colnorm(zl, N, L, part, rl, st));
+    MV_CHECK(launch_colnorm(zk, M, L, part + pl, rk, st));
+  }
+  TIMED("match");
+  MV_CHECK(launch_match(zl, N, zk, M, L, k, order, ctx->cfg.metric, ctx->cfg.reciprocal, rl, rk, split_len, splits,
+                        dist_out, ws_val, ws_idx, top_val, top_idx, st));
+  return MVAE_OK;
 }
 
 static int reconstruct_any(mvae_ctx* ctx, const float* x, const mvae_pairs* pairs, const float* eps, float* y_out,
@@ -2553,7 +2661,10 @@ extern "C" int mvae_debug_conv2(int S1, int B, int mode, int mfma, const float* 
 
 // The batch's bit operands on caller buffers (tests only; synchronous; allocates nothing): mode 0
 // launch_make_batch into x then launch_deint_bits (no_xbw: its variant 7), mode 1
-// launch_pairs_bits. S x S images, B rows. Caller buffers, zero-filled (padding is never written):
+// launch_pairs_bits; mode 2 launch_images_bits (the embedding pass's kernel): `locks` is the one
+// table, idx holds 3B entries (the images of stacked rows 0 .. 3B - 1: three index arrays of B),
+// keys and coef are not read; mode 3 the step's de-interleave alone on the caller's x (the
+// reference of mode 2: x built by the host). S x S images, B rows. Caller buffers, zero-filled (padding is never written):
 // xbf bitmat_words(3B, D + 1) words, xbw bitmat_words(D + 1, 3B) words, xbits [B][ldbits] bytes,
 // dyn 4 ints, plane [3B][ldx] bf16 (plane 0, written when the not-binary word rises), x [B][3D]
 // floats (mode 0 only).
@@ -2561,8 +2672,9 @@ extern "C" int mvae_debug_pairs_bits(const unsigned char* locks, const unsigned 
                                      const float* coef, int B, int S, float divisor, int mode, int no_xbw,
                                      float* x, unsigned* xbf, unsigned* xbw, unsigned char* xbits, int ldbits,
                                      int* dyn, unsigned short* plane, int ldx, void* stream) {
-  if (!locks || !keys || !idx || !coef || B <= 0 || S <= 0 || S > 4096 || !(divisor > 0.f) || mode < 0 || mode > 1 ||
-      (mode == 0 && !x) || !xbf || !xbw || !xbits || !dyn || !plane || ldx < S * S || ldbits < (S * S + 7) / 8)
+  const bool pairs_mode = mode == 0 || mode == 1;
+  if ((mode != 3 && (!locks || !idx)) || (pairs_mode && (!keys || !coef)) || B <= 0 || S <= 0 || S > 4096 ||
+      !(divisor > 0.f) || mode < 0 || mode > 3 || ((mode == 0 || mode == 3) && !x) || !xbf || !xbw || !xbits || !dyn || !plane || ldx < S * S || ldbits < (S * S + 7) / 8)
     return fail(nullptr, MVAE_EINVAL, "mvae_debug_pairs_bits: bad argument");
   hipStream_t st = (hipStream_t)stream;
   const int D = S * S;
@@ -2574,9 +2686,16 @@ extern "C" int mvae_debug_pairs_bits(const unsigned char* locks, const unsigned 
     if (e == hipSuccess)
       e = launch_deint_bits(x, B, D, xbf, kts_f, xbw, kts_w, xbits, ldbits, dyn, dyn + 1, nullptr, pl, ldx, 0, st,
                             no_xbw ? 7 : 0);
-  } else {
+  } else if (mode == 1) {
     e = launch_pairs_bits(locks, keys, S, S, idx, coef, divisor, B, xbf, kts_f, xbw, kts_w, xbits, ldbits, dyn,
                           dyn + 1, nullptr, pl, ldx, 0, no_xbw != 0, st);
+  } else if (mode == 2) {
+    e = launch_images_bits(locks, S, S, idx, 3 * B, divisor, B, xbf, kts_f, xbw, kts_w, xbits, ldbits, dyn, dyn + 1,
+                           nullptr, pl, ldx, 0, no_xbw != 0, st);
+  } else {
+    e = (D % 8) || (B % 64) || (ldx % 8) ? hipErrorInvalidValue
+                                         : launch_deint_bits(x, B, D, xbf, kts_f, xbw, kts_w, xbits, ldbits, dyn, dyn + 1,
+                                                             nullptr, pl, ldx, 0, st, no_xbw ? 7 : 0);
   }
   if (e == hipErrorInvalidValue)
     return fail(nullptr, MVAE_EINVAL, "mvae_debug_pairs_bits: shape or alignment the kernels do not serve");

@@ -296,6 +296,31 @@ hipError_t launch_pairs_bits(const unsigned char* locks, const unsigned char* ke
                              const float* coef, float div, int B, unsigned* xbf, int kts_f, unsigned* xbw,
                              int kts_w, unsigned char* xbits, int ldbits, int* dyn, int* dyn_next, float* xs,
                              const Planes& xp, int ldx, int f32dyn_mask, bool no_xbw, hipStream_t st);
+// ---- an embedding pass's operand from one uint8 image table (images_bits.hip) ----
+// 3B independent images, image t of the pass = row t of the stacked operand (block t / B, batch row
+// t % B): table image idx[t] (t when idx is null) for t < nvalid, an all-zero image past that (idx
+// not read). launch_images_bits writes what launch_images_x followed by launch_deint_bits writes
+// (no_xbw: variant 7) and serves D % 8 == 0, B % 64 == 0 and an 8-byte aligned table
+// (images_bits_fits; hipErrorInvalidValue otherwise, before anything is launched); launch_images_x
+// writes the pass as X [B][3 D]: x[b, 3 p + ch] = image((1, 0, 2)[ch] B + b)[p] / div.
+bool images_bits_fits(const unsigned char* table, int B, int D);
+hipError_t launch_images_bits(const unsigned char* table, int H, int W, const int* idx, int nvalid, float div, int B,
+                              unsigned* xbf, int kts_f, unsigned* xbw, int kts_w, unsigned char* xbits, int ldbits,
+                              int* dyn, int* dyn_next, float* xs, const Planes& xp, int ldx, int f32dyn_mask,
+                              bool no_xbw, hipStream_t st);
+hipError_t launch_images_x(const unsigned char* table, int H, int W, const int* idx, int nvalid, float div, int B,
+                           float* x, hipStream_t st);
+// ---- all-pairs distance with fused top-k (match.hip) ----
+// match_plan: key rows per split (a multiple of 64) and the number of splits of M for N lock rows.
+void match_plan(long long N, long long M, long long* split_len, int* splits);
+// r[l] = 1 / sqrt(max(sum_rows z[row][l]^2, 1e-12)) in a fixed order; part: match_colnorm_chunks(n) L doubles
+int match_colnorm_chunks(long long n);
+hipError_t launch_colnorm(const float* z, long long n, int L, double* part, float* r, hipStream_t st);
+// top_val / top_idx [N][k] (1 <= k <= min(M, 64)); dist null or [N][M]; ws_val / ws_idx [N][splits][k]
+// (splits > 1); rl / rk: the cosine metric's reciprocal column norms (metric 0)
+hipError_t launch_match(const float* zl, long long N, const float* zk, long long M, int L, int k, int order,
+                        int metric, int recip, const float* rl, const float* rk, long long split_len, int splits,
+                        float* dist, float* ws_val, int* ws_idx, float* top_val, int* top_idx, hipStream_t st);
 // ---- conv-encoder tower (conv_tower.hip, conv_mfma.hip) ----
 // NHWC fp32 activations of the stacked batch (3B forward rows, 4B backward rows); S = image
 // side, S1 = S/2 (after pool 1), S2 = S/4 (after pool 2).

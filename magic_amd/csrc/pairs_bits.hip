@@ -67,13 +67,7 @@ __device__ __forceinline__ PairBytes pair_load(const PairRow& row, int H, int W,
 }
 // ... and the octet's 24 values as X would store them: per pixel (lock, rotated lock, key) / div
 __device__ __forceinline__ void pair_values(const PairBytes& p, float div, float (&e)[24]) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int sh = 8 * (j & 3);
-    e[3 * j] = (float)(((j < 4 ? p.l.x : p.l.y) >> sh) & 0xFFu) / div;
-    e[3 * j + 1] = (float)(((j < 4 ? p.r.x : p.r.y) >> sh) & 0xFFu) / div;
-    e[3 * j + 2] = (float)(((j < 4 ? p.k.x : p.k.y) >> sh) & 0xFFu) / div;
-  }
+  deint_byte_values(p.l, p.r, p.k, div, e);
 }
 
 // deint_bits_kernel<2, 256, 72>'s task (64 batch rows x 128 pixels per workgroup; thread tid owns

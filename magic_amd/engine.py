@@ -288,6 +288,60 @@ class Engine:
         self._check(self.lib.mvae_generate(self.ctx, _ptr(z), n, _ptr(out), self.stream))
         return out
 
+    # ------------------------------------------------------------------ retrieval
+    def embed(self, table: torch.Tensor, idx: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+              log_sigma: bool = False, normalize: bool = True):
+        """Latent means ``[count, L]`` of single images of a uint8 table ``[n, S, S]``: the images
+        ``idx`` (int32, each in ``[0, n)``: the caller's precondition) or all ``n`` in order.
+        ``log_sigma``: returns ``(means, log-sigmas)``; then ``out`` is that pair too. ``normalize``:
+        pixels / 255, as ``PairBatch``. Any ``count >= 1``: ``ceil(count / 3B)`` encoder passes."""
+        if not table.is_cuda or table.dtype != torch.uint8 or table.dim() != 3:
+            raise ValueError("embed: a device uint8 table [n, S, S] expected")
+        # (a view into a larger storage is fine as long as its images are dense)
+        if table.stride() != (table.shape[1] * table.shape[2], table.shape[2], 1):
+            raise ValueError("embed: the table's images must be dense (use .contiguous())")
+        if idx is not None:
+            if not idx.is_cuda or idx.dtype != torch.int32 or idx.dim() != 1 or not idx.is_contiguous():
+                raise ValueError("embed: idx must be a contiguous int32 device vector")
+        count = int(table.shape[0] if idx is None else idx.shape[0])
+        if count < 1:
+            raise ValueError("embed: no image to embed")
+        L = self.cfg.latent
+        mean, ls = (out if log_sigma else (out, None)) if out is not None else (None, None)
+        mean = mean if mean is not None else torch.empty(count, L, device=self.dev)
+        if log_sigma and ls is None:
+            ls = torch.empty(count, L, device=self.dev)
+        for t in (mean, ls):
+            if t is not None and tuple(t.shape) != (count, L):
+                raise ValueError(f"embed: outputs must be [{count}, {L}]")
+        im = _lib.mvae_images()
+        im.table = table.data_ptr()
+        im.height, im.width = int(table.shape[1]), int(table.shape[2])
+        im.idx = None if idx is None else idx.data_ptr()
+        im.divisor = 255.0 if normalize else 1.0
+        self._check(self.lib.mvae_embed_images(self.ctx, C.byref(im), count, _ptr(mean), _ptr(ls), self.stream))
+        return (mean, ls) if log_sigma else mean
+
+    def match(self, zl: torch.Tensor, zk: torch.Tensor, k: int, order: int = 1, dist: bool = False):
+        """The ``k`` best keys of every lock under the model's distance (``cfg.metric``,
+        ``cfg.reciprocal``) between embeddings ``zl [N, L]`` and ``zk [M, L]``: ``(values [N, k],
+        indices [N, k] int32)``, best first -- ``order`` +1 the largest score, -1 the smallest; ties
+        by the smaller index, NaN last. ``dist``: also the whole ``[N, M]`` score matrix."""
+        L = self.cfg.latent
+        if zl.dim() != 2 or zk.dim() != 2 or zl.shape[1] != L or zk.shape[1] != L:
+            raise ValueError(f"match: embeddings must be [N, {L}] and [M, {L}]")
+        N, M = int(zl.shape[0]), int(zk.shape[0])
+        if N < 1 or M < 1 or not 1 <= int(k) <= min(M, 64):
+            raise ValueError("match: N, M >= 1 and 1 <= k <= min(M, 64) expected")
+        if order not in (1, -1):
+            raise ValueError("match: order must be +1 or -1")
+        val = torch.empty(N, int(k), device=self.dev)
+        ind = torch.empty(N, int(k), device=self.dev, dtype=torch.int32)
+        d = torch.empty(N, M, device=self.dev) if dist else None
+        self._check(self.lib.mvae_match(self.ctx, _ptr(zl), N, _ptr(zk), M, int(k), int(order), _ptr(d), _ptr(val),
+                                        ind.data_ptr(), self.stream))
+        return (val, ind, d) if dist else (val, ind)
+
     # ------------------------------------------------------------------ timing regions
     def timing_enable(self, on: bool = True):
         self._check(self.lib.mvae_timing_enable(self.ctx, int(on)))

@@ -98,6 +98,14 @@ def train(vae, batches, n_samples: int, training_epochs: int = 60, driver: str =
     return vae, history
 
 
+def retrieve_report(vae, batches, k: int, log=print):
+    """The ``--retrieve K`` report over the stream's lock / key tables; returns the ``Retrieval``."""
+    from . import retrieval
+    r = retrieval.retrieve(vae, batches.locks, batches.keys, k, normalize=batches.normalize)
+    log(retrieval.report(r))
+    return r
+
+
 def main(argv=None):
     from .vae import TangoEncoder
     ap = argparse.ArgumentParser()
@@ -113,6 +121,9 @@ def main(argv=None):
     ap.add_argument("--fused-input", action="store_true",
                     help="feed the step PairBatch descriptions of the batches (inputs(fused=True)): the "
                          "same batches and results without the float32 X array")
+    ap.add_argument("--retrieve", type=int, default=0, metavar="K",
+                    help="after training, embed the loaded lock / key tables, score every lock against "
+                         "every key and print hit@1 / hit@K of key i for lock i (K <= 64)")
     args = ap.parse_args(argv)
     cfg = preset(args.preset, image_size=args.image_size, batch=args.batch or None)
     eight_c = args.preset in ("8c", "8d", "8e", "8f")
@@ -123,6 +134,8 @@ def main(argv=None):
     t0 = time.time()
     train(vae, batches, max(args.samples_per_epoch, cfg.batch), args.epochs, driver=driver)
     print(f"done in {time.time() - t0:.1f}s", file=sys.stderr)
+    if args.retrieve > 0:
+        retrieve_report(vae, batches, args.retrieve)
     vae.close()
 
 

@@ -33,6 +33,10 @@ from .engine import Engine
 from .overlap_input import PairBatch
 
 
+def _host_array(a):
+    return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a
+
+
 def _default_config() -> MVAEConfig:
     # 11a/vae.py:30-65 with the FLAGS of 11a/constants.py
     return preset("11a", image_size=FLAGS.IMAGE_SIZE, batch=FLAGS.BATCH_SIZE,
@@ -133,6 +137,39 @@ class TangoEncoder(object):
     def reconstruct(self, X, overlap_areas=None, eps=None):
         e = None if eps is None else self._dev(eps, (3, self.batch_size, self.latent_dimensions))
         return self.engine.reconstruct(self._x(X), e).cpu().numpy()
+
+    # ----------------------------------------------------------------- retrieval
+    def _table(self, table):
+        """A uint8 image table on the device. Any other dtype is refused, not cast: a float table in
+        [0, 1] would silently become all 0 / 1."""
+        if not isinstance(table, torch.Tensor):
+            table = np.asarray(table)
+        if table.dtype not in (torch.uint8, np.uint8):
+            raise ValueError(f"embed: a uint8 image table (0..255) expected, got {table.dtype}")
+        if isinstance(table, torch.Tensor):
+            return table.to(device=self.engine.dev).contiguous()
+        return torch.from_numpy(np.ascontiguousarray(table)).to(self.engine.dev)
+
+    def embed(self, table, idx=None, normalize: bool = True):
+        """Latent means ``[count, L]`` (numpy) of single images: the uint8 table ``[n, S, S]``
+        (0..255, as the lock / key tables of the input pipeline), all of it or the images ``idx``."""
+        t = self._table(table)
+        i = None
+        if idx is not None:
+            i = torch.as_tensor(np.asarray(_host_array(idx), dtype=np.int64))
+            if i.numel() and (int(i.min()) < 0 or int(i.max()) >= t.shape[0]):
+                raise ValueError("embed: idx out of the table's range")
+            i = i.to(device=self.engine.dev, dtype=torch.int32).contiguous()
+        return self.engine.embed(t, i, normalize=normalize).cpu().numpy()
+
+    def match(self, z_locks, z_keys, k: int = 1, order: int = 1, return_dist: bool = False):
+        """``(values [N, k], indices [N, k])`` of the ``k`` best keys of every lock under the model's
+        distance between the embeddings (``order`` +1 largest first, -1 smallest first), plus the
+        ``[N, M]`` matrix of every score when ``return_dist``."""
+        zl = self._dev(z_locks, (-1, self.latent_dimensions))
+        zk = self._dev(z_keys, (-1, self.latent_dimensions))
+        out = self.engine.match(zl, zk, k, order=order, dist=return_dist)
+        return tuple(o.cpu().numpy() for o in out)
 
     # ----------------------------------------------------------------- extras
     def parameters(self):

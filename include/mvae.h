@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define MVAE_ABI_VERSION 6
+#define MVAE_ABI_VERSION 7
 #define MVAE_MAX_ENC 8
 
 enum { MVAE_OK = 0, MVAE_EINVAL = -1, MVAE_ECONFIG = -2, MVAE_ESTATE = -3 };
@@ -385,6 +385,18 @@ int mvae_debug_pairs_bits(const unsigned char* locks, const unsigned char* keys,
 int mvae_debug_gemm(int M, int N, int K, const float* A, int lda, int at, const float* B, int ldb,
                     int bt, float* C, int ldc, int epi, int act, const float* aux, int ld_aux,
                     void* stream);
+/* The fused hidden-layer chain (enc_chain.hip) on caller data (tests; synchronous; allocates nothing).
+ * x [M][ldx] bf16, layer l: w[l] [K[l]][ldw[l]] bf16 -> out[l] [M][ldo[l]] bf16. K, N, ldw, ldo, w, out are
+ * HOST arrays of nl entries holding device pointers / sizes. rows: 0 auto, or 16..96 (multiple of 16).
+ * out[l] = act(in_l w[l]) with in_0 = x and in_l = out[l-1] (so K[l] = N[l-1] + 1 in the step); column
+ * N[l] of out[l] is 1.0 (the next layer's bias input), columns up to round8(N[l] + 1) are 0, nothing
+ * else is written. Columns K[0] .. ldx - 1 of x must be zero. act: 0 tanh, 1 elu. MVAE_EINVAL with a
+ * message, before any HIP call: nl outside 1..4, M < 1, K[l] outside 1..512 (K[0] <= ldx), N[l]
+ * outside 1..511, a stride that is not a multiple of 8, ldw[l] < round8(N[l]),
+ * ldo[l] < round8(N[l] + 1), a null or not 16-byte aligned pointer, another act, a bad rows. */
+int mvae_debug_chain(int M, int nl, const int* K, const int* N, int act, int rows,
+                     const unsigned short* x, int ldx, const unsigned short* const* w, const int* ldw,
+                     unsigned short* const* out, const int* ldo, void* stream);
 
 #ifdef __cplusplus
 }

@@ -2703,3 +2703,44 @@ extern "C" int mvae_debug_pairs_bits(const unsigned char* locks, const unsigned 
   if (e != hipSuccess) { g_create_err = hipGetErrorString(e); return (int)e; }
   return MVAE_OK;
 }
+
+// The fused hidden-layer chain on caller buffers (tests only; synchronous; allocates nothing): fills a
+// ChainArgs as plan()'s chain_of does and launches the step's kernel. Everything the kernel's
+// addressing relies on is checked here, before any HIP call: it reads 16-B chunks of x up to
+// min(ldx, 512) columns, of W_l up to round8(N_l) columns of its K_l rows, and writes
+// round8(N_l + 1) columns of out_l's first M rows.
+extern "C" int mvae_debug_chain(int M, int nl, const int* K, const int* N, int act, int rows,
+                                const unsigned short* x, int ldx, const unsigned short* const* w,
+                                const int* ldw, unsigned short* const* out, const int* ldo, void* stream) {
+  auto bad = [](const std::string& m) { return fail(nullptr, MVAE_EINVAL, "mvae_debug_chain: " + m); };
+  auto misaligned = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
+  if (nl < 1 || nl > 4) return bad("nl must be in [1, 4]");
+  if (M < 1) return bad("M must be at least 1");
+  if (act != 0 && act != 1) return bad("act must be 0 (tanh) or 1 (elu)");
+  if (rows != 0 && (rows < 16 || rows > 96 || rows % 16))
+    return bad("rows must be 0 or a multiple of 16 in [16, 96]");
+  if (!K || !N || !w || !ldw || !out || !ldo) return bad("null K, N, w, ldw, out or ldo array");
+  if (!x || misaligned(x)) return bad("x is null or not 16-byte aligned");
+  if (ldx < 8 || (ldx & 7)) return bad("ldx must be a positive multiple of 8");
+  ChainArgs ca;
+  ca.x = x; ca.ldx = ldx; ca.M = M; ca.nl = nl; ca.act = act; ca.rows = rows;
+  for (int l = 0; l < nl; ++l) {
+    const std::string at = " (layer " + std::to_string(l) + ")";
+    if (K[l] < 1 || K[l] > 512) return bad("K must be in [1, 512]" + at);
+    if (N[l] < 1 || N[l] > 511) return bad("N must be in [1, 511]" + at);
+    if (l == 0 && K[0] > ldx) return bad("K[0] exceeds ldx");
+    if ((ldw[l] & 7) || ldw[l] < ((N[l] + 7) & ~7))
+      return bad("ldw must be a multiple of 8, at least round8(N)" + at);
+    if ((ldo[l] & 7) || ldo[l] < ((N[l] + 8) & ~7))
+      return bad("ldo must be a multiple of 8, at least round8(N + 1)" + at);
+    if (!w[l] || misaligned(w[l])) return bad("w is null or not 16-byte aligned" + at);
+    if (!out[l] || misaligned(out[l])) return bad("out is null or not 16-byte aligned" + at);
+    ChainLayer& cl = ca.l[l];
+    cl.w = w[l]; cl.ldw = ldw[l]; cl.K = K[l]; cl.N = N[l]; cl.out = out[l]; cl.ldo = ldo[l];
+  }
+  hipStream_t st = (hipStream_t)stream;
+  hipError_t e = launch_enc_chain(ca, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) { g_create_err = std::string("mvae_debug_chain: ") + hipGetErrorString(e); return (int)e; }
+  return MVAE_OK;
+}

@@ -1,6 +1,6 @@
 """CPU-side checks of the retrieval entry points' bindings: ``mvae_embed_images`` and ``mvae_match``
 are declared in ``include/mvae.h``, bound in ``magic_amd/_lib.py`` with the header's arity, and the
-binding's ABI version is the header's (6)."""
+binding's ABI version is the header's (7)."""
 import ctypes
 import os
 import re
@@ -15,10 +15,10 @@ def header():
     return src, re.sub(r"/\*.*?\*/", "", src, flags=re.S)
 
 
-def test_abi_version_is_6_and_matches_header():
+def test_abi_version_is_7_and_matches_header():
     raw, _ = header()
-    assert int(re.search(r"#define MVAE_ABI_VERSION (\d+)", raw).group(1)) == _lib.ABI_VERSION == 6
-    assert _lib.load().mvae_abi_version() == 6
+    assert int(re.search(r"#define MVAE_ABI_VERSION (\d+)", raw).group(1)) == _lib.ABI_VERSION == 7
+    assert _lib.load().mvae_abi_version() == 7
 
 
 def test_retrieval_entry_points_are_bound_with_the_header_arity():

@@ -42,6 +42,16 @@ def test_enc_chain_step_widths(enc, act, batch, latent):
     check_step(cfg, adam=False, **BF16)
 
 
+@pytest.mark.parametrize("rows", [48, 80])
+def test_enc_chain_step_rows_48_80(rows):
+    """The two row-block instantiations no other step runs (MB = 3 and 5: three and two weight
+    steps in LDS) at a small ragged shape, both chains planned by chain_of with the forced rows
+    (300 stacked rows, 100 decoder rows: the last workgroup's block is partly past M)."""
+    cfg = preset("8d", image_size=24, batch=100, precision="bf16").replace(
+        enc=(400, 300, 260), latent=16, options=f"enc_chain_rows={rows}")
+    check_step(cfg, adam=False, **BF16)
+
+
 @pytest.mark.parametrize("latent,dec,act,batch", [(200, (500, 500), "tanh", 4096), (16, (400, 300), "elu", 100),
                                                   (31, (511, 200), "tanh", 37), (8, (64, 500), "tanh", 1000)])
 def test_dec_chain_step(latent, dec, act, batch):

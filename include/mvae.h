@@ -333,6 +333,66 @@ int mvae_embed_images(mvae_ctx* ctx, const mvae_images* images, int64_t count, f
 int mvae_match(mvae_ctx* ctx, const float* zl, int64_t N, const float* zk, int64_t M, int k, int order,
                float* dist_out, float* top_val, int* top_idx, void* stream);
 
+/* ---- retrieval at gallery scale: a gallery in shards, fixed norms, key ranks --------------
+ * Additive to ABI 7 (the loader's build id rejects a stale library). mvae_match is unchanged. All
+ * five use the context's match workspace under mvae_match's growth rule; every invalid argument
+ * is MVAE_EINVAL with a message starting with the entry point's name, before any launch or
+ * allocation.
+ *
+ * Column sums of squares of a gallery in fp64, shard by shard: colsq [L] device doubles.
+ * accumulate 0: colsq = this call's sum; 1: colsq += it. The n rows are summed as mvae_match sums
+ * them (256-row chunks from row 0, four row quarters per column in turn, then the chunks in order
+ * onto the running value). A gallery fed in shards whose row counts are multiples of 256 (the
+ * last one free) therefore gives the bits of one call over all of it; other shard sizes agree to
+ * fp64 rounding. n >= 1. */
+int mvae_match_colsq(mvae_ctx* ctx, const float* z, int64_t n, double* colsq, int accumulate, void* stream);
+/* rnorm[l] = (float)(1 / sqrt((double)max((float)colsq[l], 1e-12f))), l < L: the reciprocal column
+ * norms mvae_match derives, bit for bit, when colsq came from mvae_match_colsq over the same rows. */
+int mvae_match_rnorm(mvae_ctx* ctx, const double* colsq, float* rnorm, void* stream);
+
+typedef struct mvae_match_opts {
+  const float *rl, *rk;   /* cosine: reciprocal column norms [L] (device) of the lock / key side; NULL:
+                             from the rows passed, as mvae_match. Each side on its own. Ignored for sqdiff. */
+  int64_t key_base;       /* global index of zk row 0: top_idx holds key_base + j; ties break on the
+                             global index; 0 <= key_base, key_base + M <= 2^31 - 1 */
+  int carry;              /* 1: top_val / top_idx (and ahead) hold the result of earlier calls on
+                             disjoint key ranges; the outputs are those of the union. 0: overwritten */
+  int64_t dist_ld;        /* row stride of dist_out in floats; 0 = M; else >= M */
+  const float* thr_val;   /* [N] \  all three or none: ahead[i] (+)= the number of keys of this call  */
+  const int* thr_idx;     /* [N]  > strictly before (thr_val[i], thr_idx[i]) in the total order of    */
+  int* ahead;             /* [N] /  `order` (score, then smaller global index; NaN last either way)   */
+} mvae_match_opts;        /* LP64: 64 bytes; offsets 0, 8, 16, 24, 32, 40, 48, 56 */
+/* mvae_match over one shard of the keys. opts NULL (or all zero) is mvae_match, except that k only
+ * needs 1 <= k <= 64: a shard may hold fewer than k keys, and unfilled entries are the empty entry
+ * (value bits 0x7FC00000, index -1), always at the end of a list. With carry the call merges its k
+ * best into the list the outputs already hold (entries of index -1 never enter), so a sweep over
+ * shards -- carry 0 on the first, 1 after -- leaves bit for bit what one mvae_match over the whole
+ * gallery returns, in any shard order, provided the shards' key ranges [key_base, key_base + M)
+ * are disjoint: that is the caller's precondition and is NOT checked (a key seen twice appears
+ * twice). For cosine presets the scores equal the one-shot call's only under the same norms: pass
+ * rl / rk computed over the whole galleries (mvae_match_colsq + mvae_match_rnorm); with fixed
+ * norms a score no longer depends on which other rows are in the call. dist_out, if given, holds
+ * this call's [N, M] block at row stride dist_ld (point it at column key_base of a wider matrix).
+ * thr_*: the count of keys before a threshold entry, fused into the scoring pass (no matrix);
+ * with (thr_val[i], thr_idx[i]) = (the score of lock i and its own key t, t) the accumulated
+ * ahead[i] is the 0-based rank of key t for lock i. carry 0 overwrites ahead, 1 adds to it.
+ * EINVAL: a null zl / zk / top_val / top_idx, N or M < 1, k outside [1, 64], order not +-1,
+ * key_base < 0, key_base + M > 2^31 - 1, carry not 0 / 1, 0 < dist_ld < M (or < 0), one or two of
+ * the thr_* trio. */
+int mvae_match_ex(mvae_ctx* ctx, const float* zl, int64_t N, const float* zk, int64_t M, int k, int order,
+                  const mvae_match_opts* opts, float* dist_out, float* top_val, int* top_idx, void* stream);
+/* Row-aligned: out[i] = the score mvae_match(_ex) gives lock row i and a key row equal to zk[i], under
+ * the same rl / rk -- the same bits, not merely close (one thread sums a row over l = 0 .. L - 1 in
+ * order with the operations of the all-pairs kernel). NULL rl / rk (each on its own): norms over the
+ * n rows passed. n >= 1. */
+int mvae_pair_scores(mvae_ctx* ctx, const float* zl, const float* zk, int64_t n, const float* rl,
+                     const float* rk, float* out, void* stream);
+/* vals / idx [N][parts][k] (empty entries: idx -1) -> the k best of each row, top_val / top_idx
+ * [N][k]: the merge step of mvae_match, for lists computed apart (other calls, other devices). The
+ * indices must be distinct within a row. N, parts >= 1, 1 <= k <= 64, order +-1. */
+int mvae_match_merge(mvae_ctx* ctx, const float* vals, const int* idx, int64_t N, int parts, int k, int order,
+                     float* top_val, int* top_idx, void* stream);
+
 /* ---- diagnostics ------------------------------------------------------------------ */
 /* HIP-event timing of named regions (one GEMM incl. its split-K reduction, or one
  * bandwidth kernel group), recorded on the launch stream while enabled.               */

@@ -58,6 +58,12 @@ class mvae_images(C.Structure):
                 ("divisor", C.c_float)]
 
 
+class mvae_match_opts(C.Structure):
+    """Options of ``mvae_match_ex`` (``include/mvae.h``): a zeroed one is ``mvae_match``."""
+    _fields_ = [("rl", C.c_void_p), ("rk", C.c_void_p), ("key_base", C.c_int64), ("carry", C.c_int),
+                ("dist_ld", C.c_int64), ("thr_val", C.c_void_p), ("thr_idx", C.c_void_p), ("ahead", C.c_void_p)]
+
+
 class mvae_tensor(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("data", C.c_void_p), ("rows", C.c_int),
                 ("cols", C.c_int), ("ld", C.c_int), ("trained_by", C.c_int)]
@@ -109,6 +115,14 @@ _SIGS = {
                           C.c_int),
     "mvae_match": ([C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p,
                     C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+    "mvae_match_colsq": ([C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p], C.c_int),
+    "mvae_match_rnorm": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+    "mvae_match_ex": ([C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int,
+                       C.POINTER(mvae_match_opts), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+    "mvae_pair_scores": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                          C.c_void_p], C.c_int),
+    "mvae_match_merge": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                          C.c_void_p, C.c_void_p], C.c_int),
     "mvae_timing_enable": ([C.c_void_p, C.c_int], C.c_int),
     "mvae_timing_select": ([C.c_void_p, C.c_int], C.c_int),
     "mvae_timing_marker": ([C.c_void_p, C.c_int, C.c_int], C.c_int),

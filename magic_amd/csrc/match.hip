@@ -15,6 +15,15 @@
 // The order is total -- (score, smaller j), NaN last for either direction -- so the k best of a row
 // are one list whatever the split; merge_kernel pushes the per-split lists through the same
 // insertion. No atomics; with dist_out null no N x M buffer exists.
+// Sharded galleries (mvae_match_ex): the key index a list holds is key_base + j, the order breaks
+// ties on that global index, and merge_kernel can start from the caller's list of earlier shards --
+// the k best over a union of disjoint key ranges are one list whatever the shards (a carried call
+// also seeds every workgroup's threshold with the k-th entry so far). The CNT
+// instantiations also count, per lock row, the keys strictly before a caller's threshold entry
+// (one more ballot and popcount per row and 64 candidates; lane r of a wave holds row r's
+// threshold and count, as the lists do); splits write their counts to the workspace and the merge
+// launch adds them in split order. pair_scores_kernel gives the row-aligned score with the very
+// operations of match_kernel's sums.
 #include "mvae_internal.h"
 
 namespace mvae {
@@ -98,13 +107,18 @@ struct MatchArgs {
   const float* rl; const float* rk;  // cosine: the reciprocal column norms
   long long split_len;               // key rows per split (a multiple of MT)
   int splits;
-  float* dist;                       // [N][M] or null
+  float* dist;                       // [N][dist_ld] or null
   float* out_val; int* out_idx;      // [N][splits][k]
+  long long dist_ld;                 // row stride of dist (>= M)
+  unsigned key_base;                 // global index of key row 0 (key_base + M < 2^31)
+  const float* thr_val; const int* thr_idx;  // CNT: [N] threshold entries (global indices)
+  int* out_cnt;                      // CNT: [N][splits] keys of the split strictly before the threshold
+  const float* seed_val; const int* seed_idx;  // carry: the list of earlier calls [N][k], else null
 };
 
 typedef float f2 __attribute__((ext_vector_type(2)));
 
-template <bool COS>
+template <bool COS, bool CNT>
 __global__ __launch_bounds__(256) void match_kernel(MatchArgs a) {
   // the operand tiles [l][row] during the k-loop, then the tile's scores [lock row][key]
   constexpr int A_WORDS = MT_K * MT_LD, B_WORDS = MT_K * MTM_LD, S_WORDS = MT * (MTM + 1);
@@ -122,6 +136,30 @@ __global__ __launch_bounds__(256) void match_kernel(MatchArgs a) {
   unsigned lj[16];
 #pragma unroll
   for (int r = 0; r < 16; ++r) { lv[r] = __uint_as_float(0x7FC00000u); lj[r] = ~0u; }
+  // carry: a key scoring worse than the k-th entry of the list so far cannot be among the k best of
+  // the union, so the lists start as k copies of that score with the empty index: the test against
+  // the k-th entry then drops such keys from the first tile on, and the copies (index -1) never
+  // enter the merge. A list so far with fewer than k entries seeds nothing.
+  if (a.seed_val) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const long long row = n0 + 16 * wave + r;
+      if (row < a.N && a.seed_idx[(size_t)row * a.k + a.k - 1] != -1) lv[r] = a.seed_val[(size_t)row * a.k + a.k - 1];
+    }
+  }
+  // CNT: lane r < 16 holds the threshold key and the running count of row 16 wave + r. The lists
+  // and the threshold index are local to this call's keys inside the kernel (the order on j is the
+  // order on key_base + j); a threshold index before / past the call's range is clamped to 0 /
+  // 2^31 - 1: no / every key of the call precedes it on a tie.
+  unsigned long long tkey = ~0ull;
+  int cnt = 0;
+  if (CNT) {
+    const long long row = n0 + 16 * wave + (lane & 15);
+    if (row < a.N) {
+      const long long t = (long long)a.thr_idx[row] - (long long)a.key_base;
+      tkey = match_key(a.thr_val[row], (unsigned)(t < 0 ? 0 : t > 0x7FFFFFFFll ? 0x7FFFFFFFll : t), a.order);
+    }
+  }
 
   for (long long m0 = mbeg; m0 < mend; m0 += MTM) {
     f2 acc[4][4];  // [lock row i][key pair: 4 tx + {0,1}, {2,3}, 64 + 4 tx + {0,1}, {2,3}]
@@ -203,7 +241,12 @@ __global__ __launch_bounds__(256) void match_kernel(MatchArgs a) {
         const int row = 16 * wave + r;
         const float s = Sc[row][64 * h + lane];
         const bool valid = jin && n0 + row < a.N;
-        if (valid && a.dist) a.dist[(n0 + row) * a.M + jc] = s;
+        if (valid && a.dist) a.dist[(n0 + row) * a.dist_ld + jc] = s;
+        if (CNT) {
+          const unsigned long long tk = __shfl(tkey, r);
+          const int c = __popcll(__ballot(valid && match_key(s, (unsigned)jc, a.order) > tk));
+          if (lane == r) cnt += c;
+        }
         topk_push(lv[r], lj[r], s, (unsigned)jc, valid, a.k, a.order);
       }
     }
@@ -214,21 +257,33 @@ __global__ __launch_bounds__(256) void match_kernel(MatchArgs a) {
     if (row < a.N && lane < a.k) {
       const size_t o = ((size_t)row * a.splits + blockIdx.y) * a.k + lane;
       a.out_val[o] = lv[r];
-      a.out_idx[o] = (int)lj[r];
+      a.out_idx[o] = lj[r] == ~0u ? -1 : (int)(a.key_base + lj[r]);  // (the global index leaves here)
     }
+  }
+  if (CNT) {
+    const long long row = n0 + 16 * wave + lane;
+    if (lane < 16 && row < a.N) a.out_cnt[(size_t)row * a.splits + blockIdx.y] = cnt;
   }
 }
 
-// one wave per lock row: the row's splits * k entries, 64 at a time in split order, through the
-// same insertion (empty entries, j = -1, never enter)
+// one wave per lock row: the caller's list of earlier calls first (carry: [N][k]), then the row's
+// splits * k entries, 64 at a time in split order, through the same insertion (empty entries,
+// j = -1, never enter). cnt [N][splits]: ahead[row] = (add ? ahead[row] : 0) + the counts in split order.
 __global__ __launch_bounds__(256) void merge_kernel(const float* __restrict__ val, const int* __restrict__ idx,
-                                                    long long N, int splits, int k, int order,
-                                                    float* __restrict__ top_val, int* __restrict__ top_idx) {
+                                                    long long N, int splits, int k, int order, int carry,
+                                                    const int* __restrict__ cnt, int add, float* top_val,
+                                                    int* top_idx, int* ahead) {
   const int lane = threadIdx.x & 63;
   const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= N) return;
   float lv = __uint_as_float(0x7FC00000u);
   unsigned lj = ~0u;
+  if (carry) {
+    const bool in = lane < k;
+    const float s = in ? top_val[(size_t)row * k + lane] : 0.f;
+    const unsigned j = in ? (unsigned)top_idx[(size_t)row * k + lane] : ~0u;
+    topk_push(lv, lj, s, j, in && j != ~0u, k, order);
+  }
   const long long n = (long long)splits * k;
   const float* v = val + (size_t)row * n;
   const int* ix = idx + (size_t)row * n;
@@ -242,6 +297,52 @@ __global__ __launch_bounds__(256) void merge_kernel(const float* __restrict__ va
     top_val[(size_t)row * k + lane] = lv;
     top_idx[(size_t)row * k + lane] = (int)lj;
   }
+  if (cnt && lane == 0) {
+    int c = add ? ahead[row] : 0;
+    for (int i = 0; i < splits; ++i) c += cnt[(size_t)row * splits + i];
+    ahead[row] = c;
+  }
+}
+
+// colsq[l] = (accumulate ? colsq[l] : 0) + the chunk sums in order: colnorm_final_kernel's sum, kept
+__global__ void colsq_sum_kernel(const double* __restrict__ part, int nchunk, int L, int accumulate,
+                                 double* __restrict__ colsq) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= L) return;
+  double s = accumulate ? colsq[c] : 0.0;
+  for (int i = 0; i < nchunk; ++i) s += part[(size_t)i * L + c];
+  colsq[c] = s;
+}
+// ... and its last line
+__global__ void rnorm_kernel(const double* __restrict__ colsq, int L, float* __restrict__ r) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= L) return;
+  r[c] = (float)(1.0 / sqrt((double)fmaxf((float)colsq[c], L2_EPS)));
+}
+
+// out[i] = score(zl[i], zk[i]): one thread per row, l = 0 .. L - 1 in order, with match_kernel's
+// operations -- cosine: the rounded products v * r, then one fma per l; sqdiff: d = a - b, then
+// fma(d, d, acc); reciprocal: 1.f / acc.
+template <bool COS>
+__global__ __launch_bounds__(64) void pair_scores_kernel(const float* __restrict__ zl, const float* __restrict__ zk,
+                                                         long long n, int L, int recip,
+                                                         const float* __restrict__ rl, const float* __restrict__ rk,
+                                                         float* __restrict__ out) {
+  const long long i = (long long)blockIdx.x * 64 + threadIdx.x;
+  if (i >= n) return;
+  const float* a = zl + (size_t)i * L;
+  const float* b = zk + (size_t)i * L;
+  float acc = 0.f;
+  for (int l = 0; l < L; ++l) {
+    if (COS) {
+      const float x = a[l] * rl[l], y = b[l] * rk[l];
+      acc = __builtin_fmaf(x, y, acc);
+    } else {
+      const float d = a[l] - b[l];
+      acc = __builtin_fmaf(d, d, acc);
+    }
+  }
+  out[i] = recip ? 1.f / acc : acc;
 }
 
 }  // namespace
@@ -269,25 +370,77 @@ hipError_t launch_colnorm(const float* z, long long n, int L, double* part, floa
   return hipGetLastError();
 }
 
+hipError_t launch_colsq(const float* z, long long n, int L, double* part, double* colsq, int accumulate,
+                        hipStream_t st) {
+  const int nchunk = match_colnorm_chunks(n);
+  hipLaunchKernelGGL(colnorm_part_kernel, dim3((L + 63) / 64, nchunk), dim3(256), 0, st, z, n, L, part);
+  hipLaunchKernelGGL(colsq_sum_kernel, dim3((L + 255) / 256), dim3(256), 0, st, part, nchunk, L, accumulate, colsq);
+  return hipGetLastError();
+}
+
+hipError_t launch_rnorm(const double* colsq, int L, float* r, hipStream_t st) {
+  hipLaunchKernelGGL(rnorm_kernel, dim3((L + 255) / 256), dim3(256), 0, st, colsq, L, r);
+  return hipGetLastError();
+}
+
+hipError_t launch_pair_scores(const float* zl, const float* zk, long long n, int L, int metric, int recip,
+                              const float* rl, const float* rk, float* out, hipStream_t st) {
+  if (!zl || !zk || !out || n < 1 || L < 1 || (metric == 0 && (!rl || !rk)) || (n + 63) / 64 > 0x7FFFFFFFll)
+    return hipErrorInvalidValue;
+  const dim3 g((unsigned)((n + 63) / 64));
+  if (metric == 0)
+    hipLaunchKernelGGL(pair_scores_kernel<true>, g, dim3(64), 0, st, zl, zk, n, L, recip, rl, rk, out);
+  else
+    hipLaunchKernelGGL(pair_scores_kernel<false>, g, dim3(64), 0, st, zl, zk, n, L, recip, rl, rk, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_match_merge(const float* vals, const int* idx, long long N, int parts, int k, int order,
+                              int carry, const int* cnt, int add, float* top_val, int* top_idx, int* ahead,
+                              hipStream_t st) {
+  if (!vals || !idx || !top_val || !top_idx || N < 1 || parts < 1 || k < 1 || k > 64 || (cnt && !ahead) ||
+      (N + 3) / 4 > 0x7FFFFFFFll)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(merge_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, vals, idx, N, parts, k, order,
+                     carry, cnt, add, top_val, top_idx, ahead);
+  return hipGetLastError();
+}
+
+hipError_t launch_match_ex(const float* zl, long long N, const float* zk, long long M, int L, int k, int order,
+                           int metric, int recip, const float* rl, const float* rk, long long split_len, int splits,
+                           float* dist, long long dist_ld, long long key_base, int carry, const float* thr_val,
+                           const int* thr_idx, int* ahead, float* ws_val, int* ws_idx, int* ws_cnt,
+                           float* top_val, int* top_idx, hipStream_t st) {
+  const bool merge = splits > 1 || carry, count = thr_val != nullptr;
+  if (!zl || !zk || N < 1 || M < 1 || L < 1 || k < 1 || k > 64 || splits < 1 || split_len % MT ||
+      split_len * splits < M || (merge && (!ws_val || !ws_idx)) || !top_val || !top_idx ||
+      (metric == 0 && (!rl || !rk)) || (N + MT - 1) / MT > 0x7FFFFFFFll || splits > 65535 ||
+      key_base < 0 || key_base + M > 0x7FFFFFFFll || dist_ld < M ||
+      (count && (!thr_idx || !ahead || (merge && !ws_cnt))))
+    return hipErrorInvalidValue;
+  MatchArgs a{zl, zk, N, M, L, k, order, metric, recip, rl, rk, split_len, splits, dist,
+              merge ? ws_val : top_val, merge ? ws_idx : top_idx, dist_ld, (unsigned)key_base,
+              thr_val, thr_idx, merge ? ws_cnt : ahead, carry ? top_val : nullptr, carry ? top_idx : nullptr};
+  const dim3 g((unsigned)((N + MT - 1) / MT), splits);
+  if (metric == 0) {
+    if (count) hipLaunchKernelGGL((match_kernel<true, true>), g, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((match_kernel<true, false>), g, dim3(256), 0, st, a);
+  } else {
+    if (count) hipLaunchKernelGGL((match_kernel<false, true>), g, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((match_kernel<false, false>), g, dim3(256), 0, st, a);
+  }
+  if (merge)
+    hipLaunchKernelGGL(merge_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, ws_val, ws_idx, N, splits, k,
+                       order, carry, count ? ws_cnt : nullptr, carry, top_val, top_idx, ahead);
+  return hipGetLastError();
+}
+
 hipError_t launch_match(const float* zl, long long N, const float* zk, long long M, int L, int k, int order,
                         int metric, int recip, const float* rl, const float* rk, long long split_len, int splits,
                         float* dist, float* ws_val, int* ws_idx, float* top_val, int* top_idx, hipStream_t st) {
-  if (!zl || !zk || N < 1 || M < 1 || L < 1 || k < 1 || k > 64 || k > M || splits < 1 || split_len % MT ||
-      split_len * splits < M || (splits > 1 && (!ws_val || !ws_idx)) || !top_val || !top_idx ||
-      (metric == 0 && (!rl || !rk)) || (N + MT - 1) / MT > 0x7FFFFFFFll || splits > 65535 ||
-      M > 0x7FFFFFFFll)
-    return hipErrorInvalidValue;
-  MatchArgs a{zl, zk, N, M, L, k, order, metric, recip, rl, rk, split_len, splits, dist,
-              splits > 1 ? ws_val : top_val, splits > 1 ? ws_idx : top_idx};
-  const dim3 g((unsigned)((N + MT - 1) / MT), splits);
-  if (metric == 0)
-    hipLaunchKernelGGL(match_kernel<true>, g, dim3(256), 0, st, a);
-  else
-    hipLaunchKernelGGL(match_kernel<false>, g, dim3(256), 0, st, a);
-  if (splits > 1)
-    hipLaunchKernelGGL(merge_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, ws_val, ws_idx, N, splits, k,
-                       order, top_val, top_idx);
-  return hipGetLastError();
+  if (k > M) return hipErrorInvalidValue;
+  return launch_match_ex(zl, N, zk, M, L, k, order, metric, recip, rl, rk, split_len, splits, dist, M, 0, 0, nullptr,
+                         nullptr, nullptr, ws_val, ws_idx, nullptr, top_val, top_idx, st);
 }
 
 }  // namespace mvae

@@ -321,6 +321,28 @@ hipError_t launch_colnorm(const float* z, long long n, int L, double* part, floa
 hipError_t launch_match(const float* zl, long long N, const float* zk, long long M, int L, int k, int order,
                         int metric, int recip, const float* rl, const float* rk, long long split_len, int splits,
                         float* dist, float* ws_val, int* ws_idx, float* top_val, int* top_idx, hipStream_t st);
+// The same over one shard of a gallery (mvae_match_ex): the lists hold key_base + j (0 <= key_base,
+// key_base + M < 2^31) and k may exceed M; dist has row stride dist_ld >= M; carry: top_val / top_idx
+// hold the list of earlier shards and the merge starts from it. thr_val / thr_idx / ahead [N] (all or
+// none): ahead[i] (carry: +=) the keys strictly before (thr_val[i], thr_idx[i]) in the order. The
+// per-split lists (and counts, ws_cnt [N][splits]) go through the workspace whenever splits > 1 or carry.
+hipError_t launch_match_ex(const float* zl, long long N, const float* zk, long long M, int L, int k, int order,
+                           int metric, int recip, const float* rl, const float* rk, long long split_len, int splits,
+                           float* dist, long long dist_ld, long long key_base, int carry, const float* thr_val,
+                           const int* thr_idx, int* ahead, float* ws_val, int* ws_idx, int* ws_cnt,
+                           float* top_val, int* top_idx, hipStream_t st);
+// merge_kernel alone: vals / idx [N][parts][k] (carry: after the list top_val / top_idx already hold);
+// cnt null or [N][parts]: ahead[i] = (add ? ahead[i] : 0) + the row's counts in order
+hipError_t launch_match_merge(const float* vals, const int* idx, long long N, int parts, int k, int order,
+                              int carry, const int* cnt, int add, float* top_val, int* top_idx, int* ahead,
+                              hipStream_t st);
+// colsq [L] doubles = (accumulate ? colsq : 0) + launch_colnorm's chunk sums in order; r = its last line
+hipError_t launch_colsq(const float* z, long long n, int L, double* part, double* colsq, int accumulate,
+                        hipStream_t st);
+hipError_t launch_rnorm(const double* colsq, int L, float* r, hipStream_t st);
+// out[i] = the score of lock row i and key row i, in match_kernel's operations
+hipError_t launch_pair_scores(const float* zl, const float* zk, long long n, int L, int metric, int recip,
+                              const float* rl, const float* rk, float* out, hipStream_t st);
 // ---- conv-encoder tower (conv_tower.hip, conv_mfma.hip) ----
 // NHWC fp32 activations of the stacked batch (3B forward rows, 4B backward rows); S = image
 // side, S1 = S/2 (after pool 1), S2 = S/4 (after pool 2).

@@ -26,6 +26,12 @@ def _ptr(t: Optional[torch.Tensor]):
     return t.data_ptr()
 
 
+def _iptr(t: torch.Tensor):
+    if not t.is_cuda or t.dtype != torch.int32 or not t.is_contiguous():
+        raise ValueError("expected a contiguous int32 device tensor")
+    return t.data_ptr()
+
+
 class Engine:
     """Owns an ``mvae_ctx``. Tensors passed in must be contiguous float32 on ``device``; wherever
     a method takes the batch ``x`` it also takes an ``overlap_input.PairBatch``."""
@@ -322,25 +328,130 @@ class Engine:
         self._check(self.lib.mvae_embed_images(self.ctx, C.byref(im), count, _ptr(mean), _ptr(ls), self.stream))
         return (mean, ls) if log_sigma else mean
 
-    def match(self, zl: torch.Tensor, zk: torch.Tensor, k: int, order: int = 1, dist: bool = False):
+    def match(self, zl: torch.Tensor, zk: torch.Tensor, k: int, order: int = 1, dist: bool = False, *,
+              rl: Optional[torch.Tensor] = None, rk: Optional[torch.Tensor] = None, key_base: int = 0,
+              carry=None, target=None, ahead: Optional[torch.Tensor] = None,
+              dist_out: Optional[torch.Tensor] = None):
         """The ``k`` best keys of every lock under the model's distance (``cfg.metric``,
         ``cfg.reciprocal``) between embeddings ``zl [N, L]`` and ``zk [M, L]``: ``(values [N, k],
         indices [N, k] int32)``, best first -- ``order`` +1 the largest score, -1 the smallest; ties
-        by the smaller index, NaN last. ``dist``: also the whole ``[N, M]`` score matrix."""
+        by the smaller index, NaN last. ``dist``: also the whole ``[N, M]`` score matrix.
+
+        A gallery in shards (``mvae_match_ex``; with none of these given the call is ``mvae_match``):
+        ``rl`` / ``rk``: the cosine metric's reciprocal column norms ``[L]`` over the whole gallery
+        (``match_rnorm(match_colsq(...))``) instead of norms over the rows passed; ``key_base``: the global index of
+        ``zk[0]``, which the indices then count from; ``carry=(val, ind)``: the lists of earlier
+        shards (disjoint key ranges: the caller's precondition), updated in place to those of the
+        union and returned; ``k`` may then exceed ``M`` (empty entries: NaN, index -1).
+        ``target=(thr_val [N], thr_idx [N] int32)``: also returns ``ahead [N]`` int32, the number of
+        this call's keys strictly before that entry in the order (added to the ``ahead`` given when
+        ``carry`` is, else overwritten). ``dist_out``: a ``[N, M]`` float32 view of unit column stride
+        (a column block of a wider matrix) the scores are written to; returned like ``dist``."""
         L = self.cfg.latent
         if zl.dim() != 2 or zk.dim() != 2 or zl.shape[1] != L or zk.shape[1] != L:
             raise ValueError(f"match: embeddings must be [N, {L}] and [M, {L}]")
         N, M = int(zl.shape[0]), int(zk.shape[0])
-        if N < 1 or M < 1 or not 1 <= int(k) <= min(M, 64):
-            raise ValueError("match: N, M >= 1 and 1 <= k <= min(M, 64) expected")
+        k = int(k)
+        ex = not (rl is None and rk is None and key_base == 0 and carry is None and target is None
+                  and ahead is None and dist_out is None)
+        if N < 1 or M < 1 or not 1 <= k <= (64 if ex else min(M, 64)):
+            raise ValueError("match: N, M >= 1 and 1 <= k <= min(M, 64) expected (k <= 64 for a shard)")
         if order not in (1, -1):
             raise ValueError("match: order must be +1 or -1")
-        val = torch.empty(N, int(k), device=self.dev)
-        ind = torch.empty(N, int(k), device=self.dev, dtype=torch.int32)
-        d = torch.empty(N, M, device=self.dev) if dist else None
-        self._check(self.lib.mvae_match(self.ctx, _ptr(zl), N, _ptr(zk), M, int(k), int(order), _ptr(d), _ptr(val),
-                                        ind.data_ptr(), self.stream))
-        return (val, ind, d) if dist else (val, ind)
+        if not ex:
+            val = torch.empty(N, k, device=self.dev)
+            ind = torch.empty(N, k, device=self.dev, dtype=torch.int32)
+            d = torch.empty(N, M, device=self.dev) if dist else None
+            self._check(self.lib.mvae_match(self.ctx, _ptr(zl), N, _ptr(zk), M, k, int(order), _ptr(d), _ptr(val),
+                                            ind.data_ptr(), self.stream))
+            return (val, ind, d) if dist else (val, ind)
+        o = _lib.mvae_match_opts()
+        for name, r in (("rl", rl), ("rk", rk)):
+            if r is not None and tuple(r.shape) != (L,):
+                raise ValueError(f"match: {name} must be [{L}]")
+        o.rl, o.rk, o.key_base = _ptr(rl), _ptr(rk), int(key_base)
+        if carry is not None:
+            val, ind = carry
+            o.carry = 1
+        else:
+            val = torch.empty(N, k, device=self.dev)
+            ind = torch.empty(N, k, device=self.dev, dtype=torch.int32)
+        if tuple(val.shape) != (N, k) or tuple(ind.shape) != (N, k):
+            raise ValueError(f"match: carry must be ([{N}, {k}] float32, [{N}, {k}] int32)")
+        d = dist_out if dist_out is not None else (torch.empty(N, M, device=self.dev) if dist else None)
+        if d is not None:
+            if (not d.is_cuda or d.dtype != torch.float32 or tuple(d.shape) != (N, M) or d.stride(1) != 1
+                    or d.stride(0) < M):
+                raise ValueError(f"match: dist_out must be a float32 device view [{N}, {M}] of unit column stride")
+            o.dist_ld = int(d.stride(0))
+        if ahead is not None and target is None:
+            raise ValueError("match: ahead needs target=(thr_val, thr_idx)")
+        if target is not None:
+            tv, ti = target
+            ahead = ahead if ahead is not None else torch.zeros(N, device=self.dev, dtype=torch.int32)
+            if tuple(tv.shape) != (N,) or tuple(ti.shape) != (N,) or tuple(ahead.shape) != (N,):
+                raise ValueError(f"match: target and ahead must be [{N}]")
+            o.thr_val, o.thr_idx, o.ahead = _ptr(tv), _iptr(ti), _iptr(ahead)
+        self._check(self.lib.mvae_match_ex(self.ctx, _ptr(zl), N, _ptr(zk), M, k, int(order), C.byref(o),
+                                           None if d is None else d.data_ptr(), _ptr(val), _iptr(ind), self.stream))
+        out = (val, ind) + ((d,) if d is not None else ())
+        return out + ((ahead,) if target is not None else ())
+
+    def match_colsq(self, z: torch.Tensor, out: Optional[torch.Tensor] = None, accumulate: bool = False):
+        """Column sums of squares ``[L]`` (float64) of the gallery rows ``z [n, L]``; ``accumulate``:
+        added onto ``out``. Shards whose row counts are multiples of 256 (the last one free) give the
+        bits of one call over the whole gallery."""
+        L = self.cfg.latent
+        if z.dim() != 2 or z.shape[1] != L or z.shape[0] < 1:
+            raise ValueError(f"match_colsq: a gallery [n, {L}] expected")
+        if out is None:
+            if accumulate:
+                raise ValueError("match_colsq: accumulate needs out")
+            out = torch.empty(L, device=self.dev, dtype=torch.float64)
+        if not out.is_cuda or out.dtype != torch.float64 or tuple(out.shape) != (L,) or not out.is_contiguous():
+            raise ValueError(f"match_colsq: out must be a contiguous float64 device vector [{L}]")
+        self._check(self.lib.mvae_match_colsq(self.ctx, _ptr(z), int(z.shape[0]), out.data_ptr(), int(bool(accumulate)),
+                                              self.stream))
+        return out
+
+    def match_rnorm(self, colsq: torch.Tensor):
+        """Reciprocal column norms ``[L]`` (float32) of ``colsq``: what ``match`` takes as ``rl`` / ``rk``."""
+        L = self.cfg.latent
+        if not colsq.is_cuda or colsq.dtype != torch.float64 or tuple(colsq.shape) != (L,) or not colsq.is_contiguous():
+            raise ValueError(f"match_rnorm: a contiguous float64 device vector [{L}] expected")
+        out = torch.empty(L, device=self.dev)
+        self._check(self.lib.mvae_match_rnorm(self.ctx, colsq.data_ptr(), _ptr(out), self.stream))
+        return out
+
+    def pair_scores(self, zl: torch.Tensor, zk: torch.Tensor, rl: Optional[torch.Tensor] = None,
+                    rk: Optional[torch.Tensor] = None):
+        """``out[i]`` = the score ``match`` gives lock row ``i`` and a key row equal to ``zk[i]`` under
+        the same ``rl`` / ``rk``, bit for bit (``None``: norms over the rows passed)."""
+        L = self.cfg.latent
+        if zl.dim() != 2 or zl.shape[1] != L or zl.shape[0] < 1 or zk.shape != zl.shape:
+            raise ValueError(f"pair_scores: two galleries [n, {L}] of equal length expected")
+        for r in (rl, rk):
+            if r is not None and tuple(r.shape) != (L,):
+                raise ValueError(f"pair_scores: rl / rk must be [{L}]")
+        out = torch.empty(zl.shape[0], device=self.dev)
+        self._check(self.lib.mvae_pair_scores(self.ctx, _ptr(zl), _ptr(zk), int(zl.shape[0]), _ptr(rl), _ptr(rk),
+                                              _ptr(out), self.stream))
+        return out
+
+    def match_merge(self, vals: torch.Tensor, idx: torch.Tensor, order: int = 1):
+        """``vals`` / ``idx [N, parts, k]`` (lists computed apart over disjoint key ranges; empty
+        entries: index -1) -> ``(values [N, k], indices [N, k])`` of their union."""
+        if vals.dim() != 3 or idx.shape != vals.shape or not 1 <= vals.shape[2] <= 64 or vals.shape[0] < 1 \
+                or vals.shape[1] < 1:
+            raise ValueError("match_merge: vals / idx [N, parts, k] with 1 <= k <= 64 expected")
+        if order not in (1, -1):
+            raise ValueError("match_merge: order must be +1 or -1")
+        N, parts, k = (int(v) for v in vals.shape)
+        val = torch.empty(N, k, device=self.dev)
+        ind = torch.empty(N, k, device=self.dev, dtype=torch.int32)
+        self._check(self.lib.mvae_match_merge(self.ctx, _ptr(vals), _iptr(idx), N, parts, k, int(order), _ptr(val),
+                                              _iptr(ind), self.stream))
+        return val, ind
 
     # ------------------------------------------------------------------ timing regions
     def timing_enable(self, on: bool = True):

@@ -98,10 +98,11 @@ def train(vae, batches, n_samples: int, training_epochs: int = 60, driver: str =
     return vae, history
 
 
-def retrieve_report(vae, batches, k: int, log=print):
-    """The ``--retrieve K`` report over the stream's lock / key tables; returns the ``Retrieval``."""
+def retrieve_report(vae, batches, k: int, log=print, shard=None, ranks: bool = False):
+    """The ``--retrieve K`` report over the stream's lock / key tables; returns the ``Retrieval``.
+    ``shard`` / ``ranks``: ``--retrieve-shard S`` / ``--retrieve-ranks``."""
     from . import retrieval
-    r = retrieval.retrieve(vae, batches.locks, batches.keys, k, normalize=batches.normalize)
+    r = retrieval.retrieve(vae, batches.locks, batches.keys, k, normalize=batches.normalize, shard=shard, ranks=ranks)
     log(retrieval.report(r))
     return r
 
@@ -124,6 +125,11 @@ def main(argv=None):
     ap.add_argument("--retrieve", type=int, default=0, metavar="K",
                     help="after training, embed the loaded lock / key tables, score every lock against "
                          "every key and print hit@1 / hit@K of key i for lock i (K <= 64)")
+    ap.add_argument("--retrieve-shard", type=int, default=0, metavar="S",
+                    help="with --retrieve: embed at most S images per call and match the keys S at a time "
+                         "(a gallery larger than the device)")
+    ap.add_argument("--retrieve-ranks", action="store_true",
+                    help="with --retrieve: also the rank of key i for lock i -- MRR and median rank")
     args = ap.parse_args(argv)
     cfg = preset(args.preset, image_size=args.image_size, batch=args.batch or None)
     eight_c = args.preset in ("8c", "8d", "8e", "8f")
@@ -135,7 +141,7 @@ def main(argv=None):
     train(vae, batches, max(args.samples_per_epoch, cfg.batch), args.epochs, driver=driver)
     print(f"done in {time.time() - t0:.1f}s", file=sys.stderr)
     if args.retrieve > 0:
-        retrieve_report(vae, batches, args.retrieve)
+        retrieve_report(vae, batches, args.retrieve, shard=args.retrieve_shard or None, ranks=args.retrieve_ranks)
     vae.close()
 
 

@@ -7,9 +7,10 @@ key ``i``; ``hit@k`` is the share of locks whose own key is among their ``k`` be
 """
 from __future__ import annotations
 
-from typing import NamedTuple
+from typing import NamedTuple, Optional
 
 import numpy as np
+import torch
 
 
 class Retrieval(NamedTuple):
@@ -19,28 +20,96 @@ class Retrieval(NamedTuple):
     hit_at_k: float
     k: int
     order: int
+    ranks: Optional[np.ndarray] = None   # [min(n, m)] keys ahead of key i for lock i (0: it is the best)
+    mrr: Optional[float] = None          # mean of 1 / (ranks + 1)
+    median_rank: Optional[float] = None  # median of ranks + 1
+
+
+def _sharded(vae, locks, keys, k, order, normalize, return_dist, shard, ranks):
+    """``retrieve`` over a gallery in pieces: at most ``shard`` images per ``embed`` call, the
+    embeddings kept on the host between the sweeps, one shard of key embeddings on the device at a
+    time; the lists carried from shard to shard, the ranks counted in the scoring pass."""
+    eng = vae.engine
+    n, m = len(locks), len(keys)
+    step = int(shard) if shard else max(n, m)
+    if step < 1:
+        raise ValueError("retrieve: shard must be at least 1")
+    zl = torch.from_numpy(np.concatenate([vae.embed(locks[i:i + step], normalize=normalize)
+                                          for i in range(0, n, step)])).to(eng.dev)
+    zk = [(j, vae.embed(keys[j:j + step], normalize=normalize)) for j in range(0, m, step)]  # host
+    up = lambda a: torch.from_numpy(a).to(eng.dev)  # noqa: E731
+    rl = rk = None
+    if vae.config.metric == "cosine":  # the norms of the whole galleries, summed shard by shard
+        cl = ck = None
+        for i in range(0, n, step):
+            cl = eng.match_colsq(zl[i:i + step], out=cl, accumulate=cl is not None)
+        for _, z in zk:
+            ck = eng.match_colsq(up(z), out=ck, accumulate=ck is not None)
+        rl, rk = eng.match_rnorm(cl), eng.match_rnorm(ck)
+    k = int(min(k, m, 64))
+    nn = min(n, m)
+    val = torch.full((n, k), float("nan"), device=eng.dev)
+    ind = torch.full((n, k), -1, device=eng.dev, dtype=torch.int32)
+    dist = torch.empty(n, m, device=eng.dev) if return_dist else None
+    target = ahead = None
+    if ranks:  # lock i's threshold entry: its score against key i, at index i (none for i >= m)
+        tv = torch.full((n,), float("nan"), device=eng.dev)
+        ti = torch.full((n,), -1, device=eng.dev, dtype=torch.int32)
+        ti[:nn] = torch.arange(nn, device=eng.dev, dtype=torch.int32)
+        for j, z in zk:
+            c = min(j + len(z), nn) - j
+            if c > 0:
+                tv[j:j + c] = eng.pair_scores(zl[j:j + c], up(z[:c]), rl, rk)
+        target, ahead = (tv, ti), torch.zeros(n, device=eng.dev, dtype=torch.int32)
+    for j, z in zk:
+        eng.match(zl, up(z), k, order=order, rl=rl, rk=rk, key_base=j, carry=(val, ind), target=target, ahead=ahead,
+                  dist_out=None if dist is None else dist[:, j:j + len(z)])
+    out = (val.cpu().numpy(), ind.cpu().numpy()) + ((dist.cpu().numpy(),) if return_dist else ())
+    return out + ((ahead[:nn].cpu().numpy(),) if ranks else ())
 
 
 def retrieve(vae, locks, keys, k: int = 10, order: int = 1, normalize: bool = True,
-             return_dist: bool = False):
+             return_dist: bool = False, shard: Optional[int] = None, ranks: bool = False):
     """``locks``, ``keys``: uint8 tables ``[n, S, S]`` and ``[m, S, S]`` (arrays or device tensors).
     Returns a ``Retrieval`` (and the ``[n, m]`` score matrix when ``return_dist``). The distance is
     trained to equal the overlap area, so the default ``order`` +1 ranks the largest predicted
     overlap first. ``hit@1`` / ``hit@k`` judge key ``i`` for lock ``i``
-    over the locks that have such a key (``i < m``)."""
-    zl = vae.embed(locks, normalize=normalize)
-    zk = vae.embed(keys, normalize=normalize)
-    k = int(min(k, len(zk), 64))
-    out = vae.match(zl, zk, k=k, order=order, return_dist=return_dist)
+    over the locks that have such a key (``i < m``).
+
+    ``shard``: embed at most that many images per call and match the keys shard by shard (only one
+    shard of key embeddings is on the device at a time); the lists are those of the one-shot call
+    (for a cosine preset bit for bit when ``shard`` is a multiple of 256, else to the rounding of
+    the fp64 column sums). ``ranks``: also, for each lock ``i < m``, how many keys rank before key
+    ``i`` (``Retrieval.ranks``, 0 = best), counted in the scoring pass without the score matrix,
+    with ``mrr`` and ``median_rank`` (1-based) of them."""
+    if shard is not None or ranks:
+        out = _sharded(vae, locks, keys, k, order, normalize, return_dist, shard, ranks)
+    else:
+        out = _one_shot(vae, locks, keys, k, order, normalize, return_dist)
     val, ind = out[0], out[1]
-    n = min(len(zl), len(zk))
+    k = val.shape[1]
+    n = min(len(val), len(keys))
     own = np.arange(n)[:, None]
     hit1 = float((ind[:n, :1] == own).any(1).mean())
     hitk = float((ind[:n] == own).any(1).mean())
-    res = Retrieval(val, ind, hit1, hitk, k, order)
+    extra = ()
+    if ranks:
+        r = out[-1].astype(np.int64)
+        extra = (r, float((1.0 / (r + 1)).mean()), float(np.median(r + 1)))
+    res = Retrieval(val, ind, hit1, hitk, k, order, *extra)
     return (res, out[2]) if return_dist else res
 
 
+def _one_shot(vae, locks, keys, k, order, normalize, return_dist):
+    zl = vae.embed(locks, normalize=normalize)
+    zk = vae.embed(keys, normalize=normalize)
+    k = int(min(k, len(zk), 64))
+    return vae.match(zl, zk, k=k, order=order, return_dist=return_dist)
+
+
 def report(r: Retrieval) -> str:
-    return (f"retrieval over {len(r.indices)} locks: hit@1 = {r.hit_at_1:.4f}, hit@{r.k} = {r.hit_at_k:.4f} "
-            f"({'largest' if r.order > 0 else 'smallest'} distance first)")
+    s = (f"retrieval over {len(r.indices)} locks: hit@1 = {r.hit_at_1:.4f}, hit@{r.k} = {r.hit_at_k:.4f} "
+         f"({'largest' if r.order > 0 else 'smallest'} distance first)")
+    if r.ranks is not None:
+        s += f", MRR = {r.mrr:.4f}, median rank = {r.median_rank:g} over {len(r.ranks)} locks"
+    return s

@@ -162,13 +162,19 @@ class TangoEncoder(object):
             i = i.to(device=self.engine.dev, dtype=torch.int32).contiguous()
         return self.engine.embed(t, i, normalize=normalize).cpu().numpy()
 
-    def match(self, z_locks, z_keys, k: int = 1, order: int = 1, return_dist: bool = False):
+    def match(self, z_locks, z_keys, k: int = 1, order: int = 1, return_dist: bool = False, rl=None, rk=None,
+              key_base: int = 0):
         """``(values [N, k], indices [N, k])`` of the ``k`` best keys of every lock under the model's
         distance between the embeddings (``order`` +1 largest first, -1 smallest first), plus the
-        ``[N, M]`` matrix of every score when ``return_dist``."""
+        ``[N, M]`` matrix of every score when ``return_dist``. ``rl`` / ``rk``: the cosine metric's
+        reciprocal column norms ``[L]`` of a whole gallery (``Engine.match_colsq`` / ``match_rnorm``) instead of
+        norms over the rows passed; ``key_base``: the index of ``z_keys[0]`` in the gallery, which the
+        returned indices count from."""
         zl = self._dev(z_locks, (-1, self.latent_dimensions))
         zk = self._dev(z_keys, (-1, self.latent_dimensions))
-        out = self.engine.match(zl, zk, k, order=order, dist=return_dist)
+        rl = None if rl is None else self._dev(rl, (self.latent_dimensions,))
+        rk = None if rk is None else self._dev(rk, (self.latent_dimensions,))
+        out = self.engine.match(zl, zk, k, order=order, dist=return_dist, rl=rl, rk=rk, key_base=key_base)
         return tuple(o.cpu().numpy() for o in out)
 
     # ----------------------------------------------------------------- extras

@@ -12,10 +12,16 @@ in one process with alternating windows (a host clock around a device synchronis
           route B: ``Engine.match``
           plus the achieved fraction of the 157 TF/s fp32 rate at 3 flops per element (sqdiff) or
           2 (cosine).
+  sharded (--sharded; record profiles/retrieval_bench_sharded_<config>.json) the same shape, L in
+          {20, 200}, both metrics:
+          one_shot: ``Engine.match`` over the 16384 keys
+          sharded:  8 shards of 2048 keys with ``key_base`` / ``carry`` (cosine: norms given)
+          ranks_off / ranks_on: one call over all keys without / with the fused count of the keys
+          before each lock's own key (cosine: norms given in both)
 
 Writes JSON under profiles/. Needs the GPU: without one it fails, it never falls back.
 
-  python tools/retrieval_bench.py --config C3 [--reps 5] [--windows 3] [--no-match] [--out ...json]
+  python tools/retrieval_bench.py --config C3 [--reps 5] [--windows 3] [--no-match] [--sharded] [--out ...json]
 """
 import argparse
 import json
@@ -143,12 +149,58 @@ def bench_match(reps, nwin, n=16384, k=10):
     return out
 
 
+def bench_sharded(reps, nwin, n=16384, k=10, shards=8):
+    out = {}
+    sync = lambda: torch.cuda.synchronize()  # noqa: E731
+    step = n // shards
+    for L in (20, 200):
+        for metric in ("sqdiff", "cosine"):
+            eng = Engine(MVAEConfig(image_size=8, batch=64, enc=(40,), dec=(28, 20), latent=L, metric=metric,
+                                    reciprocal=False, precision="f32"), 0)
+            g = torch.Generator(device="cuda").manual_seed(L)
+            zl = torch.randn(n, L, device="cuda", generator=g)
+            zk = torch.randn(n, L, device="cuda", generator=g)
+            order = 1 if metric == "cosine" else -1
+            rl = rk = None
+            if metric == "cosine":
+                rl, rk = eng.match_rnorm(eng.match_colsq(zl)), eng.match_rnorm(eng.match_colsq(zk))
+            tv = eng.pair_scores(zl, zk, rl, rk)
+            ti = torch.arange(n, device="cuda", dtype=torch.int32)
+            ahead = torch.zeros(n, device="cuda", dtype=torch.int32)
+
+            def sharded():
+                carry = None
+                for j in range(0, n, step):
+                    carry = eng.match(zl, zk[j:j + step], k, order=order, rl=rl, rk=rk, key_base=j, carry=carry)
+                return carry
+
+            routes = {"one_shot": lambda: eng.match(zl, zk, k, order=order),
+                      "sharded": sharded,
+                      "ranks_off": lambda: eng.match(zl, zk, k, order=order, rl=rl, rk=rk),
+                      "ranks_on": lambda: eng.match(zl, zk, k, order=order, rl=rl, rk=rk, target=(tv, ti), ahead=ahead)}
+            res = {r: fn() for r, fn in routes.items()}
+            sync()
+            equal = all(bool(torch.equal(res[r][0].view(torch.int32), res["one_shot"][0].view(torch.int32))
+                             and torch.equal(res[r][1], res["one_shot"][1])) for r in routes)
+            w = windows(routes, reps, nwin, sync)
+            out[f"L{L}_{metric}"] = {
+                "windows": w, "lists_bitwise_equal_to_one_shot": equal,
+                "sharded_over_one_shot": round(w["sharded"]["median"] / w["one_shot"]["median"], 3),
+                "ranks_on_over_off": round(w["ranks_on"]["median"] / w["ranks_off"]["median"], 3),
+                "mean_rank_of_own_key": round(float(res["ranks_on"][2].float().mean()), 1)}
+            print(f"sharded L={L} {metric}: " + ", ".join(f"{r} {w[r]['median']} ms" for r in routes), flush=True)
+            eng.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="C3", choices=["C2", "C3"])
     ap.add_argument("--reps", type=int, default=5, help="calls per window")
     ap.add_argument("--windows", type=int, default=3, help="windows per route (alternating)")
     ap.add_argument("--no-match", action="store_true", help="the embedding comparison only")
+    ap.add_argument("--sharded", action="store_true",
+                    help="the sharded-sweep and ranks legs only (record retrieval_bench_sharded_<config>.json)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -159,12 +211,16 @@ def main():
            "order": "A B " * a.windows, "device": torch.cuda.get_device_name(0),
            "note": "ms per call: host clock around a device synchronise, per window; kernel: HIP events; bytes: "
                    "algorithmic, from shapes"}
-    rec["embed"] = bench_embed(cfg, a.reps, a.windows)
-    print(json.dumps(rec["embed"]), flush=True)
-    if not a.no_match:
-        rec["match"] = bench_match(a.reps, a.windows)
+    if a.sharded:
+        rec["order"] = "one_shot sharded ranks_off ranks_on " * a.windows
+        rec["sharded"] = bench_sharded(a.reps, a.windows)
+    else:
+        rec["embed"] = bench_embed(cfg, a.reps, a.windows)
+        print(json.dumps(rec["embed"]), flush=True)
+        if not a.no_match:
+            rec["match"] = bench_match(a.reps, a.windows)
     out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
-                                f"retrieval_bench_{a.config.lower()}.json")
+                                f"retrieval_bench{'_sharded' if a.sharded else ''}_{a.config.lower()}.json")
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
     with open(out, "w") as f:
         json.dump(rec, f, indent=1)

@@ -134,22 +134,14 @@ int mvae_create(const mvae_cfg* cfg, int device, mvae_ctx** out);
  * writes BitMats instead of the bf16 plane and the eight-phase kernel expands the A fragments in
  * registers; a batch with another pixel value takes the planes; default 1), bits_reg (0/1: each
  * wave loads its A words straight to registers, else through an LDS copy of the block; default
- * 1), deint_fuse (0/1: the de-interleave's workers inside the layer-0 forward's launch beside its
- * tiles, handing chunks over by counters; measured slower, default 0), xbw_split (0/1/2: the
- * weight gradient's BitMat transposed from the forward's on the side stream instead of written by
- * the de-interleave; 2 = where the layer-0 forward leaves CUs idle, default), adam_nt (0/1: Adam's
- * moments and fp32 parameters stored non-temporal, default 1), e8_prio (0-2, A/B: the eight-phase
- * kernel's s_setprio form, default 0), deint_variant (0-6 or 8, A/B: the de-interleave's form; 8 = coalesced X loads through LDS), cs_one
+ * 1), xbw_split (0/1/2: the weight gradient's BitMat transposed from the forward's on the side
+ * stream instead of written by the de-interleave; 2 = where the layer-0 forward leaves CUs idle,
+ * default), adam_nt (0/1: Adam's moments and fp32 parameters stored non-temporal, default 1), cs_one
  * (0-2: the cosine metric's column statistics in one launch, the last row chunk's workgroup
  * summing the partials in the two-launch order -- the same bits; 2, the default: where L <= 32),
  * x3 (0-2: f32x ring-kernel plans on the plane-stacked kernels, every operand plane of a k-tile in
  * LDS at once -- 1 the tile-N-128 plans, 2 also the 256x256 ones; the same products summed in
- * another order; default 2). Diagnostics, results
- * meaningless: deint_fuse_diag (0-31: parts of the fused launch switched off), diag_skip_deint (1: de-interleave only the first batch -- a timing bound),
- * diag_shadow_deint (-1 or a workgroup count > 0: a second de-interleave of each step's input
- * into a scratch image on a low-priority stream, launched at diag_shadow_at = 0 the forward,
- * 1 the backward, 2 the encoder backward -- the cost of staging), diag_chain (enc_chain's
- * ablations: 1 no weight DMA past the first steps, 2 no MFMAs, 4 no copy-out; bits combine).
+ * another order; default 2). Every option computes valid results.
  * An unknown name or a value out of range is MVAE_EINVAL. The library reads no environment
  * variables (the diagnostics entry point mvae_bench_gemm aside). */
 int mvae_create_ex(const mvae_cfg* cfg, int device, const char* options, mvae_ctx** out);
@@ -253,7 +245,7 @@ int mvae_make_batch(const unsigned char* locks, const unsigned char* keys, int h
  *
  * Direct path: where the context de-interleaves a 0/1 batch to bits in a launch of its own (bf16 /
  * f32x precision with the default "bits" and "e8" plans, FC encoder, batch % 64 == 0,
- * image_size^2 % 8 == 0, no deint_fuse and no diag_* option) and both tables are 8-byte aligned,
+ * image_size^2 % 8 == 0) and both tables are 8-byte aligned,
  * one kernel writes the layer-0 bit operands straight from the tables (timing region
  * "pairs_bits"): 2 table bytes read per pixel triple instead of 12 bytes of X written and read
  * back. In every other configuration the twin materialises X into a context-owned [B, 3 D] fp32
@@ -291,8 +283,8 @@ int mvae_reconstruct_pairs(mvae_ctx* ctx, const mvae_pairs* pairs, const float* 
  * not read for them and nothing is written to the outputs past row count - 1.
  *
  * Direct path: exactly where the *_pairs twins take theirs (bf16 / f32x precision with the default
- * "bits" and "e8" plans, FC encoder, batch % 64 == 0, image_size^2 % 8 == 0, no deint_fuse and no
- * diag_* option) and the table is 8-byte aligned, one kernel writes the layer-0 bit operand from
+ * "bits" and "e8" plans, FC encoder, batch % 64 == 0, image_size^2 % 8 == 0) and the table is
+ * 8-byte aligned, one kernel writes the layer-0 bit operand from
  * the table with three 8-byte loads per pixel octet (timing region "images_bits"). Every other
  * configuration materialises the pass as X -- x[b, 3 p + ch] = image((1, 0, 2)[ch] B + b)[p] /
  * divisor, the channel of stacked block 0, 1, 2 being the rotated lock's, the lock's, the key's --
@@ -417,8 +409,10 @@ int mvae_timing_reset(mvae_ctx* ctx);
 int mvae_bench_gemm(int M, int N, int K, int at, int bt, int batch, int variant, int iters,
                     void* stream, float* avg_ms);
 /* Diagnostics: the step's de-interleave of a [B][3D] batch of random 0/1 pixels, iters launches
- * (B % 64 == 0, D % 8 == 0): variant 0-4 the bits forms (the pixel operand as BitMats), 100 the
- * bf16-plane pass. Average ms per launch in *avg_ms.                                         */
+ * (B % 64 == 0, D % 8 == 0): variant 0 the step's bits form (the pixel operand as BitMats), 7 the
+ * same without the weight-gradient words (the xbw_split form), 100 the bf16-plane pass; + 1000 four
+ * X images in turn, + 2000 / + 4000 a GEMM / memset heater before each launch. Any other variant is
+ * MVAE_EINVAL. Average ms per launch in *avg_ms.                                              */
 int mvae_bench_deint(int B, int D, int variant, int iters, void* stream, float* avg_ms);
 /* One 5x5x64x64 conv kernel of the conv tower on caller data (tests; synchronous): S1 x S1 x 64
  * NHWC images, B rows (3B forward images, 4B backward). mode 0: relu(conv(x, W2) + b2), 3B

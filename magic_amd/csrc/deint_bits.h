@@ -1,14 +1,12 @@
 // The de-interleave to bits, one task (64 batch rows x 64 PB pixels): the body of
-// deint_bits_kernel (mvae_kernels.hip) and of the worker workgroups of the layer-0 forward's
-// fused launch (gemm_bf16e.hip, DeintJob). Writes the layer-0 pixel operand of a 0/1 batch as the
+// deint_bits_kernel (mvae_kernels.hip). Writes the layer-0 pixel operand of a 0/1 batch as the
 // eight-phase kernel's BitMats (mvae_internal.h): xbf = A of the forward (rows [rot | lock | key] x
 // pixels, the ones column at k = D), xbw = A of the weight gradient (pixels x rows, the ones row at
 // pixel D), plus the BCE target (the lock block) as bits per row (GemmEpi::xbits) -- 1.1 bits
 // written per pixel triple instead of the 48 of the bf16 plane. Each thread reads 4 x 96
 // contiguous bytes (8 pixels of one row, as the plane kernel), writes one byte per block into LDS
 // ([block][octet][row]: a row-contiguous 8 x 8 bit block is one u64), then assembles the forward
-// words four at a time (one 16-B store; SC1: written through, `sc1`, for a consumer in the same
-// launch -- MI355X_MICROARCH.md's sc1 hand-off) and the weight-gradient words one at a time.
+// words four at a time (one 16-B store) and the weight-gradient words one at a time.
 // Raises the not-binary word (dyn[2]) when a pixel is neither 0 nor 1. Padding outside the
 // written blocks (rows past 3B, pixel quarters past D) is zero from the buffers' creation.
 #pragma once
@@ -40,7 +38,7 @@ struct DeintShape {
   static constexpr int NR = 64 / RPP;  // row passes per thread
   static_assert(NT % NO == 0 && 64 % RPP == 0, "whole rows per pass");
 };
-template <int PB, int NT, bool NTL = false>
+template <int PB, int NT>
 __device__ __forceinline__ void deint_load(const float4* __restrict__ x, int D, int bx, int by,
                                            float4 (&v)[DeintShape<PB, NT>::NR][6]) {
   using S = DeintShape<PB, NT>;
@@ -52,47 +50,9 @@ __device__ __forceinline__ void deint_load(const float4* __restrict__ x, int D, 
   for (int i = 0; i < S::NR; ++i) {
     const float4* src = x + ((size_t)(b0 + tid / S::NO + S::RPP * i) * 3 * D + 3 * (size_t)pix) / 4;
 #pragma unroll
-    for (int k = 0; k < 6; ++k) {
-      if constexpr (NTL) {  // (read once: non-temporal)
-        typedef float f4 __attribute__((ext_vector_type(4)));
-        const f4 t = __builtin_nontemporal_load(reinterpret_cast<const f4*>(src + k));
-        v[i][k] = make_float4(t.x, t.y, t.z, t.w);
-      } else {
-        v[i][k] = src[k];
-      }
-    }
+    for (int k = 0; k < 6; ++k) v[i][k] = src[k];
   }
 }
-// The same registers loaded coalesced: pass i's 16 rows x 96 float4 (the task's 1.5 KB of each row)
-// read by consecutive lanes (one 1 KB contiguous span per wave instruction, where deint_load's
-// lanes stride 96 B: each instruction then touches 48 lines of 128 B), passed through an LDS stage
-// (two buffers of 24 KB, pass parity) into deint_load's mapping (row tid / 16 + 16 i, octet
-// tid % 16). PB 2, 256 threads only. Float4s past the row's end (pixels past D, unused) read its last.
-__device__ __forceinline__ void deint_load_co(const float4* __restrict__ x, int D, int bx, int by,
-                                              float4 (&v)[4][6], float4 (*stage)[16][96]) {
-  const int tid = threadIdx.x;
-  const int b0 = by * 64, c40 = 3 * (bx * 128) / 4, rowf4 = 3 * D / 4;
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-      const int q = tid + 256 * k, r = q / 96, c4 = min(c40 + q % 96, rowf4 - 1);
-      v[i][k] = x[(size_t)(b0 + 16 * i + r) * rowf4 + c4];
-    }
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    float4 (*st)[96] = stage[i & 1];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-      const int q = tid + 256 * k;
-      st[q / 96][q % 96] = v[i][k];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < 6; ++k) v[i][k] = st[tid / 16][6 * (tid % 16) + k];
-  }
-}
-
 // bf16 bits of v rounded to nearest even, and the exact remainder v - bf16(v)
 __device__ __forceinline__ unsigned short bf16_rn(float v, float& rem) {
   const unsigned short b = __builtin_bit_cast(unsigned short, __float2bfloat16(v));
@@ -212,10 +172,10 @@ __device__ __forceinline__ void deint_byte_values(const uint2& l, const uint2& r
 
 // the task's BitMat words from its LDS bytes, by threads t0, t0 + nt, ...: the forward words four
 // at a time (lanes 2 q, 2 q + 1 of the fragment layout, words j = 0 / 1 each: rows 16 (2 j + h) +
-// (lane & 15), k-octet 8 kk + 4 kh + (lane >> 4); one 16-B store, SC1 written through), the
+// (lane & 15), k-octet 8 kk + 4 kh + (lane >> 4); one 16-B store), the
 // weight-gradient words one at a time (pixel 64 kk + 16 (2 j + h) + (lane & 15), rows 32 kh +
 // 8 (lane >> 4) + 0..7: bit (pixel & 7) of 8 row bytes of one octet)
-template <int PB, int OS, bool SC1, bool NOW = false>
+template <int PB, int OS, bool NOW = false>
 __device__ __forceinline__ void deint_words(int t0, int nt, int B, int D, int kts_f, int kts_w,
                                             unsigned* __restrict__ xbf, unsigned* __restrict__ xbw, int bx,
                                             int by, const DeintLds<PB, OS>& bt) {
@@ -238,15 +198,9 @@ __device__ __forceinline__ void deint_words(int t0, int nt, int B, int D, int kt
       w4[q] = w;
     }
     unsigned* dst = xbf + ((size_t)(grow >> 8) * kts_f + kt) * BITMAT_BLOCK_WORDS + ((grow >> 6) & 3) * 128 + wl0;
-    if constexpr (SC1) {
-      typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-      const u32x4 val = {w4[0], w4[1], w4[2], w4[3]};
-      asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(dst), "v"(val) : "memory");
-    } else {
-      *reinterpret_cast<uint4*>(dst) = make_uint4(w4[0], w4[1], w4[2], w4[3]);
-    }
+    *reinterpret_cast<uint4*>(dst) = make_uint4(w4[0], w4[1], w4[2], w4[3]);
   }
-  for (int wi = t0; wi < (NOW ? 0 : 3 * PB * 128); wi += nt) {  // (NOW: diagnostics, no xbw)
+  for (int wi = t0; wi < (NOW ? 0 : 3 * PB * 128); wi += nt) {  // (NOW: no xbw)
     const int c = wi / (PB * 128), kk = (wi / 128) % PB, wl = wi & 127, lane = wl >> 1, j = wl & 1;
     const int grow = c * B + b0;
     const int pq = p0 + 64 * kk;
@@ -292,7 +246,7 @@ __device__ __forceinline__ unsigned deint_pad(int pix, int D) {
 }
 // The rest of a task once every thread has put its octets (nb: this thread saw a value not 0 / 1):
 // the not-binary word, the workgroup's synchronisation, the BitMat words
-template <int PB, int NT, int OS, bool SC1, class FW, class FS, bool NOW = false>
+template <int PB, int NT, int OS, class FW, class FS, bool NOW = false>
 __device__ __forceinline__ void deint_tail(bool nb, int B, int D, int kts_f, int kts_w, unsigned* __restrict__ xbf,
                                            unsigned* __restrict__ xbw, int* __restrict__ dyn, int bx, int by,
                                            const DeintLds<PB, OS>& bt, FW&& written, FS&& synced) {
@@ -304,10 +258,10 @@ __device__ __forceinline__ void deint_tail(bool nb, int B, int D, int kts_f, int
   }
   __syncthreads();
   synced();
-  deint_words<PB, OS, SC1, NOW>(tid, NT, B, D, kts_f, kts_w, xbf, xbw, bx, by, bt);
+  deint_words<PB, OS, NOW>(tid, NT, B, D, kts_f, kts_w, xbf, xbw, bx, by, bt);
 }
 
-template <int PB, int NT, int OS, bool SC1, class FW, class FS, bool NOW = false>
+template <int PB, int NT, int OS, class FW, class FS, bool NOW = false>
 __device__ __forceinline__ void deint_finish(int B, int D, int kts_f, int kts_w, unsigned* __restrict__ xbf,
                                              unsigned* __restrict__ xbw, unsigned char* __restrict__ xbits,
                                              int ldbits, int* __restrict__ dyn, int bx, int by,
@@ -329,26 +283,20 @@ __device__ __forceinline__ void deint_finish(int B, int D, int kts_f, int kts_w,
                          v[i][4].x, v[i][4].y, v[i][4].z, v[i][4].w, v[i][5].x, v[i][5].y, v[i][5].z, v[i][5].w};
     nb |= deint_octet_put<PB, OS>(in, pad, e, xbits + (size_t)(b0 + r) * ldbits + (pix >> 3), bt, o, r);
   }
-  deint_tail<PB, NT, OS, SC1, FW, FS, NOW>(nb, B, D, kts_f, kts_w, xbf, xbw, dyn, bx, by, bt, written, synced);
+  deint_tail<PB, NT, OS, FW, FS, NOW>(nb, B, D, kts_f, kts_w, xbf, xbw, dyn, bx, by, bt, written, synced);
 }
 
 // the whole task (the standalone kernel's workgroup)
-template <int PB, int NT, int OS, bool NTL = false, bool NOW = false, bool CO = false>
+template <int PB, int NT, int OS, bool NOW = false>
 __device__ __forceinline__ void deint_bits_task(const float4* __restrict__ x, int B, int D, int kts_f, int kts_w,
                                                 unsigned* __restrict__ xbf, unsigned* __restrict__ xbw,
                                                 unsigned char* __restrict__ xbits, int ldbits,
-                                                int* __restrict__ dyn, int bx, int by, DeintLds<PB, OS>& bt,
-                                                float4 (*stage)[16][96] = nullptr) {
+                                                int* __restrict__ dyn, int bx, int by, DeintLds<PB, OS>& bt) {
   float4 v[DeintShape<PB, NT>::NR][6];
-  if constexpr (CO) {
-    static_assert(PB == 2 && NT == 256, "the coalesced load serves the step's task shape");
-    deint_load_co(x, D, bx, by, v, stage);
-  } else {
-    deint_load<PB, NT, NTL>(x, D, bx, by, v);
-  }
+  deint_load<PB, NT>(x, D, bx, by, v);
   auto none = [] {};
-  deint_finish<PB, NT, OS, false, decltype(none)&, decltype(none)&, NOW>(B, D, kts_f, kts_w, xbf, xbw, xbits,
-                                                                         ldbits, dyn, bx, by, v, bt, none, none);
+  deint_finish<PB, NT, OS, decltype(none)&, decltype(none)&, NOW>(B, D, kts_f, kts_w, xbf, xbw, xbits, ldbits, dyn, bx,
+                                                                  by, v, bt, none, none);
 }
 
 }  // namespace mvae

@@ -188,26 +188,22 @@ __global__ __launch_bounds__(CT, 1) void enc_chain_kernel(ChainArgs a) {
     else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_setprio(1);
-    if (!(a.diag & 2)) {
 #pragma unroll
-      for (int rb = 0; rb < H; ++rb)
+    for (int rb = 0; rb < H; ++rb)
 #pragma unroll
-        for (int nb = 0; nb < 4; ++nb)
-          acc[rb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[rb], fb[nb], acc[rb][nb], 0, 0, 0);
-    }
+      for (int nb = 0; nb < 4; ++nb)
+        acc[rb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[rb], fb[nb], acc[rb][nb], 0, 0, 0);
     __builtin_amdgcn_sched_barrier(0);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
-    if (!(a.diag & 2)) {
 #pragma unroll
-      for (int rb = H; rb < MB; ++rb)
+    for (int rb = H; rb < MB; ++rb)
 #pragma unroll
-        for (int nb = 0; nb < 4; ++nb)
-          acc[rb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[rb], fb[nb], acc[rb][nb], 0, 0, 0);
-    }
+      for (int nb = 0; nb < 4; ++nb)
+        acc[rb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[rb], fb[nb], acc[rb][nb], 0, 0, 0);
     __builtin_amdgcn_s_setprio(0);
     bar();  // step g's image (and, at a layer's end, the activation block) no longer read
-    if (g + NS < G && !(a.diag & 1)) issue();
+    if (g + NS < G) issue();
     if (++s < steps(l)) continue;
     // ---- layer l done: act(acc) -> the activation block (bf16, RN), padding past N
     const ChainLayer& w = a.l[l];
@@ -233,7 +229,7 @@ __global__ __launch_bounds__(CT, 1) void enc_chain_kernel(ChainArgs a) {
       const int nch = (w.N + 8) >> 3;  // chunks holding columns 0 .. N
       const int tot = TM * nch;
 #pragma unroll 1
-      for (int i = tid; i < tot && !(a.diag & 4); i += CT) {
+      for (int i = tid; i < tot; i += CT) {
         const int r = i / nch, c = i - r * nch;
         if (m0 + r < a.M) {
           const uint4 v = *reinterpret_cast<const uint4*>(act + r * AROW + 8 * (c ^ (r & 15)));

@@ -36,7 +36,6 @@
 //     conflict-free (the 16 lanes of a group: 4 k-rows x 4 row quads; the two groups of a
 //     32-lane half: k-rows 8 apart, slots XORed by 2).
 #include "gemm_common.h"
-#include "deint_bits.h"
 
 #include <cstdint>
 
@@ -200,8 +199,7 @@ __device__ __forceinline__ void bits_expand(u32x2 w, bf16x8 (&fa)[8]) {
 // the step). BITS: A from a BitMat, its fragments expanded in registers per wave (the plane
 // path's A images, reads and DMA unused) -- 1: each k-tile's block copied into LDS by one
 // 256-B LDS-DMA per wave, each wave reading its two quarters from there; 2: each wave loads its
-// two quarters' words straight into registers (two 8-B `sc1` loads per lane), the form of the
-// fused de-interleave's consumers (DeintJob)
+// two quarters' words straight into registers (two 8-B `sc1` loads per lane)
 template <bool AT, bool BT, bool ST = false, int BITS = 0>
 struct E8 {
   static constexpr bool KA = !AT, KB = BT;  // operand images k-contiguous?
@@ -227,10 +225,9 @@ struct E8 {
   unsigned bA;
   u32x2 wb0, wb1;
   // BITS 2: the words of quarters 0 / 1 (each reloaded for the next k-tile right after its
-  // expansion: quarter 0 in p1, quarter 1 in p3), this lane's 8-B index in a block (quarter 0), and
-  // the chunks known finished by the fused de-interleave
+  // expansion: quarter 0 in p1, quarter 1 in p3) and this lane's 8-B index in a block (quarter 0)
   u32x2 wn0, wn1;
-  int wq, ready;
+  int wq;
   // BITS: the 2 KB block of k-tile kt into bits buffer Bf, 256 B per wave
   template <int Bf>
   __device__ __forceinline__ void issue_bits(const Tile& t, int kt) {
@@ -243,41 +240,12 @@ struct E8 {
     wb0 = rd_b64<Bf * 2048>(bA);
     wb1 = rd_b64<Bf * 2048 + 1024>(bA);
   }
-  // BITS 2: a fused launch's chunk c is finished (the workers' done[c] reached B / 64): one `sc1`
-  // poll of the next 64 chunks' counters per try (lane i: chunk c + i), so one poll that finds
-  // the workers ahead covers every chunk they finished
-  __device__ __forceinline__ void gate(const PParams& pp, int c) {
-    if (c < ready) return;
-    const int lane = threadIdx.x & 63;
-    const int R = pp.dj.B >> 6;
-    const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-    for (;;) {
-      const int ci = c + lane;
-      const int v = ci < pp.dj.nchunks ? __hip_atomic_load(pp.dj.done + ci, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-                                       : R;
-      const unsigned long long ok = __ballot(v >= R);
-      if (ok & 1ull) {
-        ready = c + (~ok ? __builtin_ctzll(~ok) : 64);
-        return;
-      }
-      // (bounded: a worker that never finished -- 0.5 s at the 100 MHz realtime clock -- raises
-      // the job's error word; the launch then ends with invalid results instead of hanging)
-      if (__builtin_amdgcn_s_memrealtime() - t0 > 50000000ull) {
-        if (lane == 0) atomicOr(pp.dj.err, 1);
-        ready = 1 << 30;
-        return;
-      }
-      __builtin_amdgcn_s_sleep(8);  // (~0.2 us: 1536 pollers stay off the counters' L2 lines)
-    }
-  }
   // BITS 2: k-tile kt's words of this wave's quarter Q into wn0 / wn1 by an 8-B `sc1` load in
   // inline asm (invisible to hipcc's waitcnt pass, which otherwise drains every load at once: the
-  // p4 / p3 waits below retire it); a fused launch first waits until the chunk is finished
+  // p4 / p3 waits below retire it)
   template <int Q>
-  __device__ __forceinline__ void load_bits(const PParams& pp, const Tile& t, int kt) {
-    const int gk = t.ks / EBK + kt;
-    if (Q == 0 && pp.dj.nworkers && !(pp.dj.diag & 1)) gate(pp, gk / DEINT_FUSE_PB);
-    const unsigned* q = Ab + (size_t)gk * BITMAT_BLOCK_WORDS + 2 * wq + 256 * Q;
+  __device__ __forceinline__ void load_bits(const Tile& t, int kt) {
+    const unsigned* q = Ab + (size_t)(t.ks / EBK + kt) * BITMAT_BLOCK_WORDS + 2 * wq + 256 * Q;
     if constexpr (Q == 0) asm volatile("global_load_dwordx2 %0, %1, off sc1" : "=v"(wn0) : "v"(q) : "memory");
     else asm volatile("global_load_dwordx2 %0, %1, off sc1" : "=v"(wn1) : "v"(q) : "memory");
   }
@@ -330,14 +298,12 @@ struct E8 {
       fb[3] = rd_tr<O + 8192>(aB[1]);
     }
   }
-  // the quadrant's 16 MFMAs once this wave's reads have landed (priority 1 around them unless
-  // flips is false: PParams::prio)
-  bool flips = true;
+  // the quadrant's 16 MFMAs once this wave's reads have landed, at priority 1
   template <int MS, int NS>
   __device__ __forceinline__ void mfma_q(const bf16x8 (&fa)[8], const bf16x8 (&fb)[4]) {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
-    if (flips) __builtin_amdgcn_s_setprio(1);
+    __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int kh = 0; kh < 2; ++kh)
 #pragma unroll
@@ -346,7 +312,7 @@ struct E8 {
         for (int nb = 0; nb < 2; ++nb)
           acc[2 * MS + (mb >> 1)][mb & 1][NS][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
               fa[2 * mb + kh], fb[2 * nb + kh], acc[2 * MS + (mb >> 1)][mb & 1][NS][nb], 0, 0, 0);
-    if (flips) __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_s_setprio(0);
     __builtin_amdgcn_sched_barrier(0);
   }
   template <int H, int Bf>
@@ -384,7 +350,7 @@ struct E8 {
         asm volatile("" : "+v"(wn0));
         bits_expand(wn0, fa0);
       }
-      if (h1 && !ka1) load_bits<0>(pp, t, kt1);
+      if (h1 && !ka1) load_bits<0>(t, kt1);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     } else if constexpr (BITS == 1) {
       // both quarters' words (the buffer is next restaged in tile it+1's p1); the whole block of
@@ -426,7 +392,7 @@ struct E8 {
         asm volatile("" : "+v"(wn1));
         bits_expand(wn1, fa1);
       }
-      if (h1 && !ka1) load_bits<1>(pp, t, kt1);
+      if (h1 && !ka1) load_bits<1>(t, kt1);
     } else if constexpr (BITS == 1) {
       if (ex) bits_expand(wb1, fa1);
     } else {
@@ -464,7 +430,7 @@ __device__ __forceinline__ void e8_tile(const PParams& pp, short* smem) {
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 2, wn = wave & 3;
-  const Tile t = tile_of_t<256, 256>(p, true, pp.dj.nworkers);
+  const Tile t = tile_of_t<256, 256>(p, true);
 
   using S = E8<AT, BT, ST, BITS>;
   S s;
@@ -492,7 +458,6 @@ __device__ __forceinline__ void e8_tile(const PParams& pp, short* smem) {
     s.bA = lds0 + (unsigned)(wm * 512 + lane * 8);  // quarter (0, wm): rows 64 wm .. of half 0
   } else if constexpr (BITS == 2) {
     s.wq = wm * 64 + lane;  // (quarter (0, wm): words 128 wm + 2 lane, + 1; quarter 1: + 256)
-    s.ready = 0;
   } else if constexpr (S::KA) {
     s.aA[0] = lds0 + frag_addr<true>(64 * wm, lane);
   } else {
@@ -513,11 +478,6 @@ __device__ __forceinline__ void e8_tile(const PParams& pp, short* smem) {
   // waves 4-7 (the second wave of every SIMD), as a scalar condition: s_barrier ignores EXEC
   // (stamped builds, diag 128: no stagger -- both halves in the same phase)
   const bool lag = __builtin_amdgcn_readfirstlane(wave) >= 4 && !(ST && (pp.diag & 128));
-  // priority (PParams::prio): 0 priority 1 around every MFMA quadrant; 1 priority 1 for the
-  // lagging half (waves 4-7) for the whole loop, no flips (cdna_hip_programming.md T5, static
-  // form); 2 no priorities
-  s.flips = pp.prio == 0;
-  if (pp.prio == 1 && lag) __builtin_amdgcn_s_setprio(1);
 
   if (total > 0) {
     // The (k-tile, pair) walk. Default: pairs innermost. reuse (f32x plane pairs): k-tiles in
@@ -554,8 +514,8 @@ __device__ __forceinline__ void e8_tile(const PParams& pp, short* smem) {
     int kt1 = c1.kt, pr1 = c1.pr, kt2 = c2.kt, pr2 = c2.pr;
     if constexpr (BITS != 0) {
       if constexpr (BITS == 2) {
-        s.template load_bits<0>(pp, t, 0);
-        s.template load_bits<1>(pp, t, 0);
+        s.template load_bits<0>(t, 0);
+        s.template load_bits<1>(t, 0);
       } else {
         s.template issue_bits<0>(t, 0);
       }
@@ -661,182 +621,18 @@ __device__ __forceinline__ void e8_tile(const PParams& pp, short* smem) {
 template <bool BT, int EPI, bool ST>
 constexpr bool has_bits = !BT && !ST && (EPI == EPI_STORE || EPI == EPI_ACT);
 
-// The fused de-interleave's workers (DeintJob). A worker workgroup takes tasks T = w, w + W, ...
-// (task T: chunk order[T / R] of 256 pixels, batch rows 64 (T % R) ..), each in 4 passes of 16
-// rows. Each pass's 16 rows x 3 KB of X (the row chunk's interleaved pixels) go HBM -> LDS by 48
-// LDS-DMA instructions of 1 KB each (6 per wave) -- whole contiguous KBs: a thread's own 96-B
-// pieces at a 96-B lane stride, the standalone kernel's loads, touch 6x the L1 lines they use and
-// held a CU to ~25 GB/s -- into a ring of 3 pass buffers, two passes in flight. Per pass each
-// thread reads one row octet (96 B) from LDS and writes its block bytes (deint_octet) into the
-// task's byte image -- no global store in a pass: the next pass's DMA wait would wait for it too
-// (vmcnt retires in order). At a task's first pass the previous task's words (deint_words;
-// forward words written through) and target bytes are stored, and counted in done[chunk] one pass
-// later, once every wave's vmcnt wait has retired them and the pass barrier has passed.
-// Measured at C3 (r6t-r6y): the workers alone 0.69 ms on their 64 CUs (the DMA alone 0.34 ms;
-// dedicated loader waves beside 4 transposing waves 0.88), so the fused launch (0.78 ms) loses
-// to the separate de-interleave + forward (0.50 ms): the transpose's VALU and LDS work per byte
-// needs more CUs than the forward's tiles leave free. Option deint_fuse stays off.
-constexpr int DW_ROWB = 64 * DEINT_FUSE_PB * 12;   // bytes of one row's 256-pixel chunk (3 KB)
-constexpr int DW_PASSB = 16 * DW_ROWB;              // one pass: 16 rows (48 KB)
-constexpr int DW_BT = 3 * 8 * DEINT_FUSE_PB * 72;   // one task's byte image (DeintLds)
-constexpr int DW_ORDER = 3 * DW_PASSB + 2 * DW_BT;  // LDS byte offset of the order table
-constexpr int DW_LDS = 163840;                      // the workgroup's LDS (160 KB)
-constexpr int DW_MAXCH = (DW_LDS - DW_ORDER) / 4;   // chunks the order table can hold
-static_assert(DW_ORDER + 4 * 64 <= DW_LDS, "LDS");
-__device__ __forceinline__ void deint_worker(const DeintJob& dj, short* smem) {
-  constexpr int PB = DEINT_FUSE_PB, OS = 72;
-  using Lds = DeintLds<PB, OS>;
-  char* lds = reinterpret_cast<char*>(smem);
-  int* ord = reinterpret_cast<int*>(lds + DW_ORDER);
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int R = dj.B >> 6;
-  const int W = dj.nworkers;
-  const int ntask = dj.nchunks * R;
-  const int D = dj.D;
-  if (blockIdx.x == 0 && tid == 0 && dj.dyn_next) {
-    dj.dyn_next[0] = 0;
-    dj.dyn_next[2] = 0;
-  }
-  for (int i = tid; i < dj.nchunks; i += ENT) ord[i] = dj.order ? dj.order[i] : i;
-  __syncthreads();
-  if ((int)blockIdx.x >= ntask) return;
-  const int ntw = (ntask - 1 - (int)blockIdx.x) / W + 1;  // this worker's tasks
-  const int P = 4 * ntw;                                   // ... and passes
-  auto task_of = [&](int k) { return (int)blockIdx.x + k * W; };
-  typedef __attribute__((address_space(3))) void* lds_ptr;
-  // pass p's 48 KB into ring buffer p % 3: this wave's instructions jj = wave + 8 m (row jj / 3,
-  // KB jj % 3 of it)
-  auto issue = [&](int p) {
-    if (dj.diag & 16) return;
-    const int T = task_of(p >> 2);
-    const int c = ord[T / R];
-    const size_t row0 = (size_t)(64 * (T % R) + 16 * (p & 3));
-    const int f0 = 3 * 256 * c;  // first float of the row chunk
-#pragma unroll
-    for (int m = 0; m < 6; ++m) {
-      const int jj = wave + 8 * m, rr = jj / 3, part = jj % 3;
-      int f = f0 + part * 256 + 4 * lane;
-      f = f + 4 <= 3 * D ? f : 3 * D - 4;  // (past the row: its last 16 B, unused)
-      const float* src = dj.x + (row0 + rr) * 3 * (size_t)D + f;
-      __builtin_amdgcn_global_load_lds(src, (lds_ptr)(lds + (p % 3) * DW_PASSB + jj * 1024), 16, 0, 0);
-    }
-  };
-  issue(0);
-  if (P > 1) issue(1);
-  // the BCE target bytes of task t (block 1 of its byte image) to xbits, four per thread: no
-  // store in the pass loop, whose next DMA wait would also wait for the store (vmcnt is in order)
-  auto target_bytes = [&](int t, const Lds& bt) {
-    const int c = ord[t / R], r = tid >> 3, o0 = 4 * (tid & 7);
-    const int q0 = 32 * c + o0, nq = D >> 3;  // first octet of the row chunk, octets per row
-    unsigned char* dst = dj.xbits + (size_t)(64 * (t % R) + r) * dj.ldbits + q0;
-    if (q0 + 4 <= nq) {
-      *reinterpret_cast<unsigned*>(dst) = (unsigned)bt[1][o0][r] | (unsigned)bt[1][o0 + 1][r] << 8 |
-                                          (unsigned)bt[1][o0 + 2][r] << 16 | (unsigned)bt[1][o0 + 3][r] << 24;
-    } else {
-      for (int j = 0; j < 4 && q0 + j < nq; ++j) dst[j] = bt[1][o0 + j][r];
-    }
-  };
-  bool nb = false;
-  int pend = -1;  // chunk of the task whose words were stored in the last pass
-  for (int p = 0; p < P; ++p) {
-    const int k = p >> 2, q = p & 3;
-    // pass p landed; what is younger: pass p+1's DMA, issued at the end of pass p-1 (the stores
-    // of pass p-1, issued before it, retire here too)
-    if (p + 1 < P) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    // (a bare barrier: __syncthreads' release fence would wait for the DMA in flight)
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    bar();
-    // (the words stored at the last pass are older than pass p+1's DMA: retired by this pass's
-    // wait in every wave)
-    if (pend >= 0) {
-      if (tid == 0 && dj.done) __hip_atomic_fetch_add(dj.done + pend, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      pend = -1;
-    }
-    const int T = task_of(k);
-    const int c = ord[T / R], by = T % R;
-    if (q == 0 && k > 0 && !(dj.diag & 8)) {  // the last task's words from its byte image
-      const int Tp = task_of(k - 1);
-      const int cp = ord[Tp / R];
-      const Lds& btp = *reinterpret_cast<const Lds*>(lds + 3 * DW_PASSB + ((k - 1) & 1) * DW_BT);
-      deint_words<PB, OS, true>(tid, ENT, dj.B, D, dj.kts_f, dj.kts_w, dj.xbf, dj.xbw, cp, Tp % R, btp);
-      target_bytes(Tp, btp);
-      pend = cp;
-    }
-    if (!(dj.diag & 8)) {
-      Lds& bt = *reinterpret_cast<Lds*>(lds + 3 * DW_PASSB + (k & 1) * DW_BT);
-      const char* raw = lds + (p % 3) * DW_PASSB;
-      const int rr = tid >> 5, o = tid & 31;
-      const int pix = 256 * c + 8 * o, r = 16 * q + rr;
-      unsigned by3[3];
-      const unsigned pad = (pix <= D && D < pix + 8) ? 1u << (D - pix) : 0u;
-      by3[0] = by3[1] = by3[2] = pad;
-      if (pix + 8 <= D) {
-        const float4* src = reinterpret_cast<const float4*>(raw + rr * DW_ROWB + o * 96);
-        float e[24];
-#pragma unroll
-        for (int t = 0; t < 6; ++t) {
-          const float4 v = src[t];
-          e[4 * t] = v.x; e[4 * t + 1] = v.y; e[4 * t + 2] = v.z; e[4 * t + 3] = v.w;
-        }
-        nb |= deint_octet(e, by3);
-      }
-#pragma unroll
-      for (int cc = 0; cc < 3; ++cc) bt[cc][o][r] = (unsigned char)by3[cc];
-    }
-    // into the buffer pass p - 1 was read from (free since the barrier), after this pass's stores
-    // (issued at the pass's start, the DMA measured slower: 0.77 vs 0.69 ms of workers at C3)
-    if (p + 2 < P) issue(p + 2);
-  }
-  // the last task: its words once every wave's bytes are in (the barrier), then its count
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  bar();
-  const int Tl = task_of(ntw - 1);
-  const int cl = ord[Tl / R];
-  if (!(dj.diag & 8)) {
-    const Lds& btl = *reinterpret_cast<const Lds*>(lds + 3 * DW_PASSB + ((ntw - 1) & 1) * DW_BT);
-    deint_words<PB, OS, true>(tid, ENT, dj.B, D, dj.kts_f, dj.kts_w, dj.xbf, dj.xbw, cl, Tl % R, btl);
-    target_bytes(Tl, btl);
-  }
-  if (dj.dyn && __ballot(nb) != 0 && lane == 0) atomicOr(dj.dyn + 2, 1);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (tid == 0 && dj.done) {
-    if (pend >= 0) __hip_atomic_fetch_add(dj.done + pend, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_fetch_add(dj.done + cl, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-}
-
-// the workers alone, one per CU (diagnostics: mvae_bench_deint variant 5; order null = identity)
-__global__ __launch_bounds__(ENT, 1) void deint_persist_kernel(DeintJob dj) {
-  __shared__ __attribute__((aligned(1024))) short smem[DW_LDS / 2];
-  deint_worker(dj, smem);
-}
-
 template <bool AT, bool BT, int EPI, bool TE, bool ST = false>
 __global__ __launch_bounds__(ENT, 1) void gemm_bf16e_kernel(PParams pp) {
   if (epi_skip<EPI>(pp.g.epi)) return;
-  if (pp.g.epi.only_if && *pp.g.epi.only_if == 0) return;
   // [A0 b0 | A0 b1 | A1 b0 | A1 b1 | B0 b0 | B0 b1 | B1 b0 | B1 b1]; the row-major epilogue's two
   // 64-row bands and the BCE row partials reuse it after the k-loop (one __shared__ array: a
   // second one can make hipcc wait vmcnt(0) before the loop's LDS reads)
   constexpr int RING = 8 * EH;
   constexpr int EPIL = 2 * (2 * 64 * 256 + 64 * 4 * 32);
-  // (the bits-path instantiations also carry the fused de-interleave's workers: the whole 160 KB)
-  constexpr int SM0 = RING > EPIL ? RING : EPIL;
-  constexpr int SM = has_bits<BT, EPI, ST> && DW_LDS / 2 > SM0 ? DW_LDS / 2 : SM0;
+  constexpr int SM = RING > EPIL ? RING : EPIL;
   __shared__ __attribute__((aligned(1024))) short smem[SM];
   // a 0/1 batch (the de-interleave's not-binary word, a uniform branch): A from its bits
   if constexpr (has_bits<BT, EPI, ST>) {
-    if (pp.dj.nworkers) {  // the fused de-interleave: workers first, then the GEMM's tiles
-      if ((int)blockIdx.x < pp.dj.nworkers) {
-        if (!(pp.dj.diag & 4)) deint_worker(pp.dj, smem);
-        return;
-      }
-      if (pp.dj.diag & 2) return;
-      e8_tile<false, BT, EPI, TE, ST, 2>(pp, smem);
-      return;
-    }
     if (pp.abits && (!pp.anb || *pp.anb == 0)) {
       if (pp.bits_reg) e8_tile<false, BT, EPI, TE, ST, 2>(pp, smem);
       else e8_tile<false, BT, EPI, TE, ST, 1>(pp, smem);
@@ -855,8 +651,7 @@ hipError_t launch_e(const PParams& p, hipStream_t st) {
       return hipGetLastError();
     }
   }
-  if (p.dj.nworkers && (!has_bits<BT, EPI, false> || AT || !p.abits || (p.dj.nworkers & 7))) return hipErrorInvalidValue;
-  hipLaunchKernelGGL((gemm_bf16e_kernel<AT, BT, EPI, TE>), dim3(nwg + p.dj.nworkers), dim3(ENT), 0, st, p);
+  hipLaunchKernelGGL((gemm_bf16e_kernel<AT, BT, EPI, TE>), dim3(nwg), dim3(ENT), 0, st, p);
   return hipGetLastError();
 }
 
@@ -872,16 +667,6 @@ template <int EPI>
 hipError_t launch_e_t(const PParams& p, bool at, bool bt, bool te, hipStream_t st) {
   return te ? launch_e_l<EPI, true>(p, at, bt, st) : launch_e_l<EPI, false>(p, at, bt, st);
 }
-
-}  // namespace
-
-hipError_t launch_deint_persist(const DeintJob& j, hipStream_t st) {
-  if (j.nworkers <= 0 || j.nchunks > DW_MAXCH || (j.B % 64) || (j.D % 8)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(deint_persist_kernel, dim3(j.nworkers), dim3(ENT), 0, st, j);
-  return hipGetLastError();
-}
-
-namespace {
 
 // (tests / diagnostics) one BitMat word per thread from a bf16 plane of 0/1 values
 __global__ void bits_from_plane_kernel(const unsigned short* __restrict__ plane, int ld, int trans, int M,

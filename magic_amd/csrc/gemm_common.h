@@ -51,9 +51,7 @@ struct PParams {
   long long abits_sb = 0;
   const int* anb = nullptr;
   int npairs_a0 = 1;                // the leading pairs with A plane 0 (the bits path's pairs)
-  DeintJob dj;                      // eight-phase kernel: the fused de-interleave (GemmDesc::dj)
   int bits_reg = 0;                 // eight-phase bits path: A words by loads to registers (E8 BITS 2)
-  int prio = 0;                     // eight-phase kernel: s_setprio form (gemm_bf16e.hip e8_tile)
   int x3 = 0;                       // f32x ring plans at tile N 128: the plane-stacked kernel (GemmDesc::x3)
 };
 
@@ -173,14 +171,11 @@ struct Tile {
   int z, bi, si, m0, n0, nt, ks, ke;
 };
 template <int TBM, int TBN>
-__device__ __forceinline__ Tile tile_of_t(const Params& p, bool remap, int boff = 0) {
+__device__ __forceinline__ Tile tile_of_t(const Params& p, bool remap) {
   Tile t;
   const int tiles = p.ntm * p.ntn;
   const int nwg = tiles * p.batch * p.split;
-  // boff: workgroups ahead of the tiles (the fused de-interleave's workers; a multiple of 8, so
-  // blockIdx % 8 still names the XCD)
-  const int bx = (int)blockIdx.x - boff;
-  const int b = remap ? xcd_remap(bx, nwg) : bx;
+  const int b = remap ? xcd_remap((int)blockIdx.x, nwg) : (int)blockIdx.x;
   t.z = b / tiles;
   const int rem = b - t.z * tiles;
   int mt;

@@ -40,15 +40,6 @@ constexpr uint64_t EVAL_STREAM = 1ull << 63;
 struct mvae_ctx {
   mvae_cfg cfg{};
   int device = 0;
-  bool diag_skip_deint = false;  // create option diag_skip_deint (timing bound only: wrong results)
-  // diagnostics (create options diag_shadow_deint / diag_shadow_at): a second de-interleave of
-  // the step's input into a scratch image on a low-priority stream beside the step -- the cost
-  // to the step of staging the next batch's pass (grid: -1 the normal launch, > 0 persistent)
-  int diag_shadow = 0, diag_shadow_at = 0;
-  hipStream_t stage = nullptr;
-  bool stage_pending = false;
-  unsigned short* shadow = nullptr;
-  const float* last_x = nullptr;
   // a batch given as (tables, idx, coefficients) (the *_pairs entry points) where the direct
   // kernel does not apply: X materialised here (launch_make_batch), allocated on first need
   float* pairs_x = nullptr;
@@ -142,22 +133,13 @@ struct mvae_ctx {
   unsigned* xbf = nullptr;
   unsigned* xbw = nullptr;
   int kts_f = 0, kts_w = 0;
-  // the de-interleave inside the layer-0 forward's launch (create option deint_fuse; DeintJob):
-  // f0f the fused launch (bits path, its own split), f0fb the plane-path fallback that runs only
-  // for a batch with a pixel other than 0 / 1; fuse_buf: the chunk counters, error word, order
   int adam_nt = 0;  // create option adam_nt
-  int deint_variant = 0;  // create option deint_variant
-  int e8_prio = 0;        // create option e8_prio (PParams::prio)
   // create option xbw_split: the de-interleave writes the forward BitMat only and the weight
   // gradient's (xbw) is transposed from it on the side stream (launch_bits_transpose), joined by
   // xbw_ev before the layer-0 weight gradient
   int xbw_split = 0;
   hipEvent_t xbw_ev = nullptr;
   bool xbw_pending = false;
-  bool fuse = false;
-  GemmDesc f0f, f0fb;
-  int* fuse_buf = nullptr;
-  int fuse_nchunks = 0;
   // schedule (each GEMM tagged with its timing region)
   std::vector<GemmDesc> fwd_enc;  // encoder layers + head
   // the hidden layers fwd_enc[1 .. nenc-1] as one launch (enc_chain.hip; create option enc_chain)
@@ -450,7 +432,6 @@ int mvae_destroy(mvae_ctx* ctx) {
   for (auto e : ctx->sync_ev) hipEventDestroy(e);
   if (ctx->xbw_ev) hipEventDestroy(ctx->xbw_ev);
   if (ctx->side) hipStreamDestroy(ctx->side);
-  if (ctx->stage) hipStreamDestroy(ctx->stage);
   for (void* p : ctx->allocs) hipFree(p);
   if (ctx->match_ws) hipFree(ctx->match_ws);
   hipSetDevice(dev);
@@ -469,21 +450,13 @@ struct CreateOpts {
   int dact_planes = 1;  // bf16 mode: DACT epilogues read the activation's bf16 plane
   int bce_split = 1;    // the BCE head in whole rounds + 256x128 ring tiles
   int plan_log = 0;     // print the GEMM plans on stderr
-  int diag_skip_deint = 0;  // diagnostics: de-interleave only the first batch (the step's time
-                            // without its streaming pass; results meaningless)
-  int diag_shadow_deint = 0, diag_shadow_at = 0;  // diagnostics: see mvae_ctx::diag_shadow
   int enc_chain = 1;    // bf16 mode: the encoder's hidden layers in one launch (0: one GEMM each)
   int enc_chain_rows = 0;  // ... its rows per workgroup forced (16..96, multiple of 16; 0 auto)
-  int diag_chain = 0;      // ... its timing ablations (ChainArgs::diag; results meaningless)
   int dec_chain = 1;    // bf16 mode: the decoder's two hidden layers in one launch (0: one GEMM each)
   int bits = 1;         // plane modes: the layer-0 pixel operand of a 0/1 batch as bits (BitMat)
   int bits_reg = 1;     // ... the eight-phase bits path loading A's words to registers (E8 BITS 2;
                         // 0: through an LDS copy -- C3 1.784 vs 1.769 ms, C5 2.450 vs 2.432, r6t)
-  int deint_fuse = 0;   // ... the de-interleave run inside the layer-0 forward's launch (DeintJob)
-  int deint_fuse_diag = 0;  // ... its timing diagnostics (DeintJob::diag; results invalid)
   int adam_nt = 1;      // Adam's moment / fp32 parameter stores non-temporal (C2 -0.6 %, C3 -0.3 %, r6za)
-  int deint_variant = 0;  // the bits de-interleave's form (launch_deint_bits; diagnostics / A-B)
-  int e8_prio = 0;      // the eight-phase kernel's s_setprio form (PParams::prio; A-B)
   int x3 = 2;           // f32x: ring plans on the plane-stacked kernels (gemm_bf16.hip): 1 the tile-N-128
                         // plans (C2 -2.1 / -2.9 % on two boxes, r6zi / r6zj), 2 also the 256x256 ones
                         // (C2's hidden weight gradients 68.5 -> 66.5 us, step -0.2 %, r6zp)
@@ -519,19 +492,11 @@ static int parse_opts(const char* s, CreateOpts* o) {
     else if (k == "dact_planes" && in(0, 1)) o->dact_planes = (int)v;
     else if (k == "bce_split" && in(0, 1)) o->bce_split = (int)v;
     else if (k == "plan_log" && in(0, 1)) o->plan_log = (int)v;
-    else if (k == "diag_skip_deint" && in(0, 1)) o->diag_skip_deint = (int)v;
-    else if (k == "diag_shadow_deint" && in(-1, 1 << 16)) o->diag_shadow_deint = (int)v;
-    else if (k == "diag_shadow_at" && in(0, 2)) o->diag_shadow_at = (int)v;
     else if (k == "enc_chain" && in(0, 1)) o->enc_chain = (int)v;
-    else if (k == "diag_chain" && in(0, 7)) o->diag_chain = (int)v;
     else if (k == "dec_chain" && in(0, 1)) o->dec_chain = (int)v;
     else if (k == "bits" && in(0, 1)) o->bits = (int)v;
     else if (k == "bits_reg" && in(0, 1)) o->bits_reg = (int)v;
-    else if (k == "deint_fuse" && in(0, 1)) o->deint_fuse = (int)v;
-    else if (k == "deint_fuse_diag" && in(0, 31)) o->deint_fuse_diag = (int)v;
     else if (k == "adam_nt" && in(0, 1)) o->adam_nt = (int)v;
-    else if (k == "deint_variant" && (in(0, 6) || v == 8)) o->deint_variant = (int)v;
-    else if (k == "e8_prio" && in(0, 2)) o->e8_prio = (int)v;
     else if (k == "xbw_split" && in(0, 2)) o->xbw_split = (int)v;
     else if (k == "cs_one" && in(0, 2)) o->cs_one = (int)v;
     else if (k == "x3" && in(0, 2)) o->x3 = (int)v;
@@ -562,13 +527,8 @@ int mvae_create_ex(const mvae_cfg* cfg, int device, const char* options, mvae_ct
   if (!ctx) return fail(nullptr, MVAE_EINVAL, "out of host memory");
   ctx->cfg = *cfg;
   ctx->device = device;
-  ctx->diag_skip_deint = opt.diag_skip_deint != 0;
   ctx->adam_nt = opt.adam_nt;
-  ctx->deint_variant = opt.deint_variant;
-  ctx->e8_prio = opt.e8_prio;
   ctx->xbw_split = opt.xbw_split == 1 ? 1 : 0;  // (2: decided with the forward's plan, below)
-  ctx->diag_shadow = opt.diag_shadow_deint;
-  ctx->diag_shadow_at = opt.diag_shadow_at;
   hipError_t he = hipSetDevice(device);
   if (he != hipSuccess) { g_create_err = hipGetErrorString(he); delete ctx; return (int)he; }
   auto c = ctx;
@@ -966,61 +926,7 @@ int mvae_create_ex(const mvae_cfg* cfg, int device, const char* options, mvae_ct
       c->f_split = true;
     }
   }
-  {  // the de-interleave inside the layer-0 forward's launch (DeintJob): the forward's 256 x 256
-     // tiles x split leave CUs free for its workers (C3: 192 tiles + 64 workers; C2: 96 tiles x
-     // split 2 + 64 workers), so its HBM stream runs beside the k-loop instead of before it
-    const GemmDesc& f0 = c->fwd_enc[0];
-    const long long tiles = (long long)((f0.M + 255) / 256) * ((f0.N + 255) / 256) * f0.batch;
-    const int kt = (f0.K + 63) / 64;
-    int sp = 0;  // the largest split whose workgroups leave >= 32 CUs (>= 8 k-tiles per slab)
-    for (int s = 1; s <= 8 && tiles * s <= 224 && (s == 1 || kt / s >= 8); ++s) sp = s;
-    int sp_plan = 0, tn = 0, tm = 0;
-    if (c->bits_on) gemm_bf16_wide_plan(f0, ~size_t(0), &sp_plan, &tn, &tm);
-    if (opt.deint_fuse && c->bits_on && sp > 0 && f0.batch == 1 && tn == GEMM_TN_E8 && !f0.at && !f0.bt &&
-        (f0.epi.mode == EPI_ACT || f0.epi.mode == EPI_STORE) && (c->D % 8) == 0 && (c->ldx % 8) == 0) {
-      const int nwg = (int)tiles * sp;
-      const int W = (256 - nwg) & ~7;
-      const int nch = (c->kts_f + DEINT_FUSE_PB - 1) / DEINT_FUSE_PB;
-      if (nch > 640) goto no_fuse;  // (the workers' LDS order table: gemm_bf16e.hip DW_MAXCH)
-      float* q = nullptr;
-      ALLOC(q, 2 * (size_t)nch + 8);
-      c->fuse_buf = reinterpret_cast<int*>(q);
-      // production order: by the slab-local k-tile at which a consumer first needs the chunk (the
-      // split-K slabs' chunks in turn), then by chunk
-      const int kcs = (kt + sp - 1) / sp;  // k-tiles per slab
-      std::vector<std::pair<int, int>> key(nch);
-      for (int ch = 0; ch < nch; ++ch) {
-        const int k0 = DEINT_FUSE_PB * ch, sl = std::min(sp - 1, k0 / kcs);
-        key[ch] = {k0 - sl * kcs, ch};
-      }
-      std::sort(key.begin(), key.end());
-      std::vector<int> order(nch);
-      for (int i = 0; i < nch; ++i) order[i] = key[i].second;
-      if (hipMemcpy(c->fuse_buf + nch + 8, order.data(), nch * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
-        g_create_err = "hipMemcpy fuse order";
-        mvae_destroy(c);
-        return MVAE_EINVAL;
-      }
-      GemmDesc f = f0;
-      f.split = sp;
-      f.variant = 13;  // the eight-phase kernel (its bits path carries the workers)
-      DeintJob& j = f.dj;
-      j.B = c->B; j.D = c->D; j.kts_f = c->kts_f; j.kts_w = c->kts_w;
-      j.xbf = c->xbf; j.xbw = c->xbw; j.xbits = c->xbits; j.ldbits = c->ldbits;
-      j.done = c->fuse_buf;
-      j.err = c->fuse_buf + nch;
-      j.order = c->fuse_buf + nch + 8;
-      j.nworkers = W;
-      j.nchunks = nch;
-      j.diag = opt.deint_fuse_diag;
-      c->f0f = f;
-      c->f0fb = f0;  // (epi.only_if: the not-binary word, set per call)
-      c->fuse_nchunks = nch;
-      c->fuse = true;
-    }
-  no_fuse:;
-  }
-  if (opt.xbw_split == 2 && c->bits_on && !c->fuse) {  // the forward's workgroups leave CUs free?
+  if (opt.xbw_split == 2 && c->bits_on) {  // the forward's workgroups leave CUs free?
     const GemmDesc& f0 = c->fwd_enc[0];
     int sp = 0, tn = 0, tm = 0;
     gemm_bf16_wide_plan(f0, ~size_t(0), &sp, &tn, &tm);
@@ -1028,10 +934,8 @@ int mvae_create_ex(const mvae_cfg* cfg, int device, const char* options, mvae_ct
                                                                    (tn == GEMM_TN_E8 ? 256 : tn)) * f0.batch;
     c->xbw_split = tiles * sp <= 224 ? 1 : 0;
   }
-  if (c->fuse) c->xbw_split = 0;  // (the fused launch's workers write xbw themselves)
   size_t ws = 0;
   auto wsz = [&](const GemmDesc& d) { ws = std::max(ws, gemm_workspace_elems(d)); };
-  if (c->fuse) wsz(c->f0f);
   for (int R : {2, 4, 8})
     for (auto& d : c->w0c[R]) wsz(d);
   for (auto& d : c->fwd_enc) wsz(d);
@@ -1055,7 +959,6 @@ int mvae_create_ex(const mvae_cfg* cfg, int device, const char* options, mvae_ct
     ca.nl = (int)ds.size();
     ca.act = d0.epi.act;
     ca.rows = opt.enc_chain_rows;
-    ca.diag = opt.diag_chain;
     bool ok = ca.nl >= 1 && ca.nl <= 4;
     const GemmDesc* prev = nullptr;
     int i = 0;
@@ -1108,12 +1011,6 @@ int mvae_create_ex(const mvae_cfg* cfg, int device, const char* options, mvae_ct
     int lo = 0, hi = 0;
     hipError_t se = hipDeviceGetStreamPriorityRange(&lo, &hi);
     if (se == hipSuccess) se = hipStreamCreateWithPriority(&c->side, hipStreamNonBlocking, lo);
-    if (se == hipSuccess && c->diag_shadow) {
-      se = hipStreamCreateWithPriority(&c->stage, hipStreamNonBlocking, lo);
-      void* q = nullptr;
-      if (se == hipSuccess) se = hipMalloc(&q, (size_t)3 * c->B * c->ldx * sizeof(unsigned short));
-      if (se == hipSuccess) { c->allocs.push_back(q); c->shadow = static_cast<unsigned short*>(q); }
-    }
     if (se == hipSuccess) se = hipEventCreateWithFlags(&c->xbw_ev, hipEventDisableTiming);
     for (int i = 0; se == hipSuccess && i < 16; ++i) {
       hipEvent_t ev = nullptr;
@@ -1303,13 +1200,6 @@ static int run(mvae_ctx* ctx, const GemmDesc& d, hipStream_t st, int r = -1) {
     if (dd.epi.xdyn == ctx->dyn) dd.epi.xdyn = ctx->dyn_cur;
     if (dd.epi.xnb == ctx->dyn + 2) dd.epi.xnb = ctx->dyn_cur + 2;
     if (dd.anb == ctx->dyn + 2) dd.anb = ctx->dyn_cur + 2;
-    dd.prio = ctx->e8_prio;
-    MV_CHECK(gemm_run(dd, ws, ctx->ws_elems, st));
-    return MVAE_OK;
-  }
-  if (ctx->e8_prio) {
-    GemmDesc dd = d;
-    dd.prio = ctx->e8_prio;
     MV_CHECK(gemm_run(dd, ws, ctx->ws_elems, st));
     return MVAE_OK;
   }
@@ -1331,11 +1221,9 @@ static int stream_wait(mvae_ctx* ctx, hipStream_t from, hipStream_t to) {
 // latent mean/log-sigma heads only (transform: no eps, no z, no column statistics).
 enum { ENC_TRAIN = 0, ENC_EVAL = 1, ENC_MEAN = 2 };
 
-static int shadow_deint(mvae_ctx* ctx, hipStream_t st);
-
 // The batch is x, or (x == NULL) the pairs descriptor. A pairs batch takes the direct kernel
 // (launch_pairs_bits: the BitMats straight from the tables) exactly where an x batch would take the
-// plain bits branch below and the launcher's shape / alignment conditions hold; in every other
+// bits branch below and the launcher's shape / alignment conditions hold; in every other
 // configuration X is materialised into the context's scratch and the x code runs on it.
 //
 // One pass of mvae_embed_images (x and pairs NULL): the 3B images [first, first + 3B) of the call,
@@ -1350,8 +1238,7 @@ struct EmbedPass {
 static int encode(mvae_ctx* ctx, const float* x, const float* eps, hipStream_t st, int draw = ENC_TRAIN,
                   const mvae_pairs* pairs = nullptr, const EmbedPass* ep = nullptr) {
   auto c = ctx;
-  const bool bits_plain = c->bits_on && !c->fuse && !c->diag_skip_deint && !c->diag_shadow;
-  const bool direct = bits_plain && ((pairs && pairs_bits_fits(pairs->locks, pairs->keys, pairs->coef, c->B, c->D)) ||
+  const bool direct = c->bits_on && ((pairs && pairs_bits_fits(pairs->locks, pairs->keys, pairs->coef, c->B, c->D)) ||
                                      (ep && images_bits_fits(ep->table, c->B, c->D)));
   if (c->side && c->side_pending) {  // an early-Adam backward whose mvae_adam never came
     c->side_pending = false;
@@ -1362,11 +1249,6 @@ static int encode(mvae_ctx* ctx, const float* x, const float* eps, hipStream_t s
   if (c->xbw_pending) {  // the last transpose read the forward BitMat this pass rewrites
     c->xbw_pending = false;
     MV_CHECK(hipStreamWaitEvent(st, c->xbw_ev, 0));
-  }
-  if (c->stage_pending) {  // (diagnostics) the last shadow pass ends before this step
-    c->stage_pending = false;
-    MV_CHECK(hipEventRecord(c->sync_ev[c->sync_next % c->sync_ev.size()], c->stage));
-    MV_CHECK(hipStreamWaitEvent(st, c->sync_ev[c->sync_next++ % c->sync_ev.size()], 0));
   }
   if ((pairs || ep) && !direct) {
     if (!c->pairs_x) {
@@ -1386,36 +1268,7 @@ static int encode(mvae_ctx* ctx, const float* x, const float* eps, hipStream_t s
     }
     x = c->pairs_x;
   }
-  c->last_x = x;
-  bool f0_done = false;  // the layer-0 forward ran with the fused de-interleave
-  if (c->fuse && !c->diag_skip_deint && !c->diag_shadow && (reinterpret_cast<uintptr_t>(x) % 16) == 0) {
-    // one launch: the de-interleave's workers beside the forward GEMM's tiles (DeintJob); then the
-    // grey pass (zeroing the chunk counters) and the forward on the planes, both returning at once
-    // for a 0/1 batch
-    int* prev = c->dyn_cur ? c->dyn_cur : c->dyn;
-    int* cur = prev == c->dyn ? c->dyn + 1 : c->dyn;
-    {
-      TIMED("deint_fwd0");
-      GemmDesc f = c->f0f;
-      f.dj.x = x;
-      f.dj.dyn = cur;
-      f.dj.dyn_next = prev;
-      if (f.dynA == c->dyn) f.dynA = cur;
-      MV_CHECK(gemm_run(f, c->ws, c->ws_elems, st));
-    }
-    {
-      TIMED("deint_grey");
-      MV_CHECK(launch_deint_grey(x, c->B, c->D, cur, c->xs, planes_of(c, c->xs), c->ldx, c->x32dyn, c->fuse_buf,
-                                 c->fuse_nchunks, st));
-      GemmDesc fb = c->f0fb;
-      if (fb.dynA == c->dyn) fb.dynA = cur;
-      fb.anb = cur + 2;
-      fb.epi.only_if = cur + 2;
-      MV_CHECK(gemm_run(fb, c->ws, c->ws_elems, st));
-    }
-    c->dyn_cur = cur;
-    f0_done = true;
-  } else if (!(c->diag_skip_deint && c->dyn_cur)) {  // (diagnostics: the stale image of the last pass)
+  {
     TimeScope ts_deint(ctx, region(ctx, direct ? (ep ? "images_bits" : "pairs_bits") : "deinterleave"), st);
     // the flag's slots alternate: this pass raises the one the previous pass zeroed and zeroes
     // the previous one (its readers are all behind on this stream), no memset launch per step
@@ -1433,8 +1286,7 @@ static int encode(mvae_ctx* ctx, const float* x, const float* eps, hipStream_t s
                                    cur, prev, c->xs, planes_of(c, c->xs), c->ldx, c->x32dyn, split, st));
       else
         MV_CHECK(launch_deint_bits(x, c->B, c->D, c->xbf, c->kts_f, c->xbw, c->kts_w, c->xbits, c->ldbits, cur,
-                                   prev, c->xs, planes_of(c, c->xs), c->ldx, c->x32dyn, st,
-                                   split ? (c->deint_variant == 8 ? 9 : 7) : c->deint_variant));
+                                   prev, c->xs, planes_of(c, c->xs), c->ldx, c->x32dyn, split, st));
       if (split) {  // xbw from xbf on the side stream, beside the layer-0 forward
         const bool two = c->use_side && c->side;
         hipStream_t sd = two ? c->side : st;
@@ -1449,10 +1301,6 @@ static int encode(mvae_ctx* ctx, const float* x, const float* eps, hipStream_t s
       MV_CHECK(launch_deinterleave(x, c->xs, planes_of(c, c->xs), cur, c->dyn ? prev : nullptr, c->B,
                                    c->D, c->ldx, c->x32mask, c->x32dyn, st, c->xbits, c->ldbits));
     c->dyn_cur = cur;
-  }
-  if (c->diag_shadow && c->diag_shadow_at == 0 && draw == ENC_TRAIN) {
-    int rc = shadow_deint(c, st);
-    if (rc) return rc;
   }
   const size_t ne = (size_t)3 * c->B * c->L;
   if (draw != ENC_MEAN) {
@@ -1491,7 +1339,7 @@ static int encode(mvae_ctx* ctx, const float* x, const float* eps, hipStream_t s
       MV_CHECK(launch_lrn2_pool2_fwd(T, nimg, c->xf, c->ldf, c->xf32, planes_of(c, c->xf), st));
     }
   }
-  for (size_t i = f0_done ? 1 : 0; i < c->fwd_enc.size(); ++i) {
+  for (size_t i = 0; i < c->fwd_enc.size(); ++i) {
     if (c->chain && i == 1) {  // the hidden layers 1 .. nenc-1
       TimeScope ts(c, c->chain_r, st);
       MV_CHECK(launch_enc_chain(c->chain_args, st));
@@ -1603,17 +1451,6 @@ extern "C" int mvae_metric(mvae_ctx* ctx, const float* areas, void* stream) {
 static int w0n(const mvae_ctx* c) { return c->w0_chunks == 1 ? 1 : (int)c->w0c[c->w0_chunks].size(); }
 static int nparts(const mvae_ctx* c) { return w0n(c) + 2; }
 
-// (diagnostics) the shadow de-interleave on the stage stream, after the work on st so far
-static int shadow_deint(mvae_ctx* ctx, hipStream_t st) {
-  auto c = ctx;
-  if (!c->last_x || !c->stage) return MVAE_OK;
-  MV_CHECK(hipEventRecord(c->sync_ev[c->sync_next % c->sync_ev.size()], st));
-  MV_CHECK(hipStreamWaitEvent(c->stage, c->sync_ev[c->sync_next++ % c->sync_ev.size()], 0));
-  MV_CHECK(launch_deinterleave_grid(c->last_x, c->shadow, c->B, c->D, c->ldx, c->diag_shadow, c->stage));
-  c->stage_pending = true;
-  return MVAE_OK;
-}
-
 // Adam's arguments for this step (TF ApplyAdam: lr_t = lr * sqrt(1 - beta2_power) /
 // (1 - beta1_power), all fp32), the whole index range
 static AdamArgs adam_args(const mvae_ctx* c) {
@@ -1633,8 +1470,6 @@ static AdamArgs adam_args(const mvae_ctx* c) {
 static int backward_part(mvae_ctx* ctx, int part, hipStream_t st, bool join_dec) {
   auto c = ctx;
   int rc;
-  if (c->diag_shadow && part == 0 && c->diag_shadow_at == 1 && (rc = shadow_deint(c, st))) return rc;
-  if (c->diag_shadow && part == 1 && c->diag_shadow_at == 2 && (rc = shadow_deint(c, st))) return rc;
   const int R = w0n(c);
   const bool two = c->use_side && c->side;
   hipStream_t sd = two ? c->side : st;
@@ -2414,9 +2249,14 @@ extern "C" int mvae_timing_reset(mvae_ctx* ctx) {
 // and filled with uniform [-1,1) values inside, `iters` launches are timed with HIP events
 // on `stream` after 3 warm-ups. variant selects a kernel variant (0 = default).
 // (diagnostics) the de-interleave of a [B][3D] batch of random 0/1 pixels (density 0.1), iters
-// launches on the stream: variant 0-4 the bits forms (launch_deint_bits), 100 the bf16-plane pass
+// launches on the stream: variant 0 the step's bits form (launch_deint_bits), 7 the same without
+// the weight-gradient words (no_xbw), 100 the bf16-plane pass; any other variant is MVAE_EINVAL
 extern "C" int mvae_bench_deint(int B, int D, int variant, int iters, void* stream, float* avg_ms) {
-  if (B <= 0 || D <= 0 || B % 64 || D % 8 || iters <= 0 || !avg_ms) return MVAE_EINVAL;
+  if (B <= 0 || D <= 0 || B % 64 || D % 8 || iters <= 0 || !avg_ms || variant < 0) return MVAE_EINVAL;
+  {
+    const int form = variant % 2000 % 1000;  // (the modifiers below taken off)
+    if (form != 0 && form != 7 && form != 100) return MVAE_EINVAL;
+  }
   hipStream_t st = (hipStream_t)stream;
   const int ldx = (D + 1 + 7) / 8 * 8, ldbits = (D / 8 + 15) & ~15;
   const int kf = bitmat_kts(D + 1), kw = bitmat_kts(3 * B);
@@ -2457,7 +2297,7 @@ extern "C" int mvae_bench_deint(int B, int D, int variant, int iters, void* stre
   auto one = [&]() -> hipError_t {
     x = xr[it++ % nx];
     if (variant == 100) return launch_deinterleave(x, xs, pl, dyn, dyn + 4, B, D, ldx, 0, 2, st, xb, ldbits);
-    return launch_deint_bits(x, B, D, xbf, kf, xbw, kw, xb, ldbits, dyn, dyn + 4, xs, pl, ldx, 2, st, variant);
+    return launch_deint_bits(x, B, D, xbf, kf, xbw, kw, xb, ldbits, dyn, dyn + 4, xs, pl, ldx, 2, variant == 7, st);
   };
   hipEvent_t t0 = nullptr, t1 = nullptr;
   if (e == hipSuccess) e = hipEventCreate(&t0);
@@ -2795,7 +2635,7 @@ extern "C" int mvae_debug_conv2(int S1, int B, int mode, int mfma, const float* 
 }
 
 // The batch's bit operands on caller buffers (tests only; synchronous; allocates nothing): mode 0
-// launch_make_batch into x then launch_deint_bits (no_xbw: its variant 7), mode 1
+// launch_make_batch into x then launch_deint_bits (no_xbw: its forward words only), mode 1
 // launch_pairs_bits; mode 2 launch_images_bits (the embedding pass's kernel): `locks` is the one
 // table, idx holds 3B entries (the images of stacked rows 0 .. 3B - 1: three index arrays of B),
 // keys and coef are not read; mode 3 the step's de-interleave alone on the caller's x (the
@@ -2819,8 +2659,8 @@ extern "C" int mvae_debug_pairs_bits(const unsigned char* locks, const unsigned 
   if (mode == 0) {
     e = launch_make_batch(locks, keys, S, S, idx, coef, B, divisor, x, st);
     if (e == hipSuccess)
-      e = launch_deint_bits(x, B, D, xbf, kts_f, xbw, kts_w, xbits, ldbits, dyn, dyn + 1, nullptr, pl, ldx, 0, st,
-                            no_xbw ? 7 : 0);
+      e = launch_deint_bits(x, B, D, xbf, kts_f, xbw, kts_w, xbits, ldbits, dyn, dyn + 1, nullptr, pl, ldx, 0,
+                            no_xbw != 0, st);
   } else if (mode == 1) {
     e = launch_pairs_bits(locks, keys, S, S, idx, coef, divisor, B, xbf, kts_f, xbw, kts_w, xbits, ldbits, dyn,
                           dyn + 1, nullptr, pl, ldx, 0, no_xbw != 0, st);
@@ -2830,7 +2670,7 @@ extern "C" int mvae_debug_pairs_bits(const unsigned char* locks, const unsigned 
   } else {
     e = (D % 8) || (B % 64) || (ldx % 8) ? hipErrorInvalidValue
                                          : launch_deint_bits(x, B, D, xbf, kts_f, xbw, kts_w, xbits, ldbits, dyn, dyn + 1,
-                                                             nullptr, pl, ldx, 0, st, no_xbw ? 7 : 0);
+                                                             nullptr, pl, ldx, 0, no_xbw != 0, st);
   }
   if (e == hipErrorInvalidValue)
     return fail(nullptr, MVAE_EINVAL, "mvae_debug_pairs_bits: shape or alignment the kernels do not serve");

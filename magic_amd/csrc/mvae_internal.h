@@ -68,40 +68,7 @@ struct GemmEpi {
   // its constant value: 1.0 at column N when padw == 2 (an activation's ones column), else 0.
   // (Element-wise stores of a partial last chunk cost ~5 us per 256x256-tile epilogue.)
   int padw = 0;
-  // the launch (and a split-K reduction's) returns at entry while *only_if == 0: the layer-0
-  // forward's plane-path fallback behind the fused de-interleave (DeintJob), which runs only for a
-  // batch with a pixel other than 0 or 1 (eight-phase kernel and split-K reductions only)
-  const int* only_if = nullptr;
 };
-
-// The de-interleave to bits run inside the layer-0 forward's launch (create option deint_fuse):
-// workgroups [0, nworkers) are workers that de-interleave tasks of 64 batch rows x 256 pixels
-// (deint_bits.h) chunk by chunk, in `order`, writing the forward BitMat through (`sc1`) and
-// counting each finished task in done[chunk] by an agent-scope atomic add after every storing
-// wave's vmcnt(0); the GEMM workgroups (the rest, tile = block - nworkers) read the BitMat's words
-// by `sc1` loads to registers, each wave after its own `sc1` poll of done[chunk] reached B / 64
-// (MI355X_MICROARCH.md's sc1 hand-off, first row). The forward GEMM's tiles x split leave
-// nworkers CUs free, so the de-interleave's HBM stream runs beside the k-loop instead of before
-// it. A wait longer than ~0.5 s raises *err and proceeds (results then invalid; never a hang).
-struct DeintJob {
-  const float* x = nullptr;
-  int B = 0, D = 0, kts_f = 0, kts_w = 0;
-  unsigned* xbf = nullptr;
-  unsigned* xbw = nullptr;
-  unsigned char* xbits = nullptr;
-  int ldbits = 0;
-  int* dyn = nullptr;
-  int* dyn_next = nullptr;
-  int* done = nullptr;         // [nchunks], zero at launch (deint_grey_kernel zeroes it after)
-  const int* order = nullptr;  // [nchunks] chunk production order (the split-K slabs' chunks in turn)
-  int* err = nullptr;
-  int nworkers = 0, nchunks = 0;  // nworkers 0: no fused de-interleave
-  int diag = 0;  // timing diagnostics (results invalid): 1 tiles do not wait, 2 tiles exit at once,
-                 // 4 workers exit at once, 8 workers' consumers idle, 16 workers' loaders idle
-};
-constexpr int DEINT_FUSE_PB = 4;  // k-tiles (64 pixels each) per chunk
-// (diagnostics) the fused launch's workers alone, j.nworkers workgroups (j.done may be null)
-hipError_t launch_deint_persist(const DeintJob& j, hipStream_t st);
 
 // bf16 operand shadows (precision = bf16). When set, the GEMM reads A/B from these
 // instead of the fp32 pointers (same logical layout/ld) and accumulates in fp32.
@@ -133,10 +100,8 @@ struct GemmDesc {
   int abits_kts = 0;
   long long abits_sb = 0;
   const int* anb = nullptr;
-  DeintJob dj;                         // the fused de-interleave (eight-phase bits path only)
   int bits_reg = 0;                    // bits path: A words by loads to registers (gemm_bf16e.hip E8)
   int x3 = 0;                          // f32x ring plans at tile N 128 on the plane-stacked kernel (gemm_bf16.hip)
-  int prio = 0;                        // eight-phase kernel: s_setprio form (PParams::prio)
   GemmEpi epi;
 };
 
@@ -195,8 +160,6 @@ struct ChainArgs {
   const unsigned short* x = nullptr;  // the first layer's input plane [M][ldx] (padded rows)
   int ldx = 0, M = 0, nl = 0, act = 0;
   int rows = 0;  // rows per workgroup forced (create option enc_chain_rows; 0: enc_chain_rows)
-  int diag = 0;  // timing ablations (results meaningless): 1 no weight DMA after the first steps,
-                 // 2 no MFMAs, 4 no block copy-out (create option diag_chain)
   ChainLayer l[4];
 };
 // rows per workgroup for M rows (a multiple of 16, <= 96; forced: a valid forced value wins)
@@ -226,20 +189,17 @@ hipError_t launch_deinterleave(const float* x, float* xs, const Planes& xp, int*
 // bitmat_kts(3B)) and the BCE target bits; *dyn slot 2 raised when a pixel is not 0 / 1, and then
 // (a gated second kernel) the planes of xp, the fp32 rows of f32dyn_mask and the inexact flag as
 // launch_deinterleave writes them. dyn_next: the other flag slot, zeroed. Both BitMats must be
-// zero-filled once (their padding is never written).
+// zero-filled once (their padding is never written). no_xbw: the forward words only
+// (launch_bits_transpose then writes xbw from xbf).
+hipError_t launch_deint_bits(const float* x, int B, int D, unsigned* xbf, int kts_f, unsigned* xbw, int kts_w,
+                             unsigned char* xbits, int ldbits, int* dyn, int* dyn_next, float* xs,
+                             const Planes& xp, int ldx, int f32dyn_mask, bool no_xbw, hipStream_t st);
 // the weight gradient's BitMat xbw from the forward's xbf (both of a 3B-row batch; see
 // bits_transpose_kernel)
 hipError_t launch_bits_transpose(const unsigned* xbf, int kts_f, unsigned* xbw, int kts_w, int B, hipStream_t st);
-// the grey pass alone (after a fused launch: also zeroes its chunk counters done[0 .. ndone))
+// the grey pass alone
 hipError_t launch_deint_grey(const float* x, int B, int D, int* dyn, float* xs, const Planes& xp, int ldx,
-                             int f32dyn_mask, int* done, int ndone, hipStream_t st);
-hipError_t launch_deint_bits(const float* x, int B, int D, unsigned* xbf, int kts_f, unsigned* xbw, int kts_w,
-                             unsigned char* xbits, int ldbits, int* dyn, int* dyn_next, float* xs,
-                             const Planes& xp, int ldx, int f32dyn_mask, hipStream_t st, int variant = 0);
-// (diagnostics) the bf16 plane-0 pass alone into xp: grid -1 the normal launch, > 0 that many
-// persistent 256-thread workgroups striding over the rows' 8-pixel groups
-hipError_t launch_deinterleave_grid(const float* x, unsigned short* xp, int B, int D, int ldx, int grid,
-                                    hipStream_t st);
+                             int f32dyn_mask, hipStream_t st);
 // N(0,1) into out[slots][B][L]: elements (s*Bg + off + b)*L + l of the counter's global stream
 // (Bg rows per slot over all ranks, this rank's rows starting at off)
 hipError_t launch_normal(float* out, int slots, int B, int L, int Bg, int off, uint64_t seed,
@@ -288,7 +248,7 @@ hipError_t launch_make_batch(const unsigned char* locks, const unsigned char* ke
 // ---- a batch's bit operands straight from the uint8 tables (pairs_bits.hip) ----
 // What launch_make_batch followed by launch_deint_bits writes (the same bits: BitMats, target
 // bits, flag slots, and for a batch with a pixel other than 0 / 1 the planes, fp32 rows and inexact
-// flag of the grey pass), without X. no_xbw: the forward words only (launch_deint_bits variant 7).
+// flag of the grey pass), without X. no_xbw: the forward words only (as launch_deint_bits').
 // Serves D = H W % 8 == 0, B % 64 == 0, 8-byte aligned tables and a 16-byte aligned coef
 // (pairs_bits_fits); hipErrorInvalidValue otherwise, before anything is launched.
 bool pairs_bits_fits(const unsigned char* locks, const unsigned char* keys, const float* coef, int B, int D);
@@ -300,7 +260,7 @@ hipError_t launch_pairs_bits(const unsigned char* locks, const unsigned char* ke
 // 3B independent images, image t of the pass = row t of the stacked operand (block t / B, batch row
 // t % B): table image idx[t] (t when idx is null) for t < nvalid, an all-zero image past that (idx
 // not read). launch_images_bits writes what launch_images_x followed by launch_deint_bits writes
-// (no_xbw: variant 7) and serves D % 8 == 0, B % 64 == 0 and an 8-byte aligned table
+// (no_xbw: likewise) and serves D % 8 == 0, B % 64 == 0 and an 8-byte aligned table
 // (images_bits_fits; hipErrorInvalidValue otherwise, before anything is launched); launch_images_x
 // writes the pass as X [B][3 D]: x[b, 3 p + ch] = image((1, 0, 2)[ch] B + b)[p] / div.
 bool images_bits_fits(const unsigned char* table, int B, int D);

@@ -128,21 +128,6 @@ __global__ void deinterleave_vecn_kernel(const float4* __restrict__ x, float* __
   }
 }
 
-// (diagnostics) persistent form: gridDim.x workgroups stride over the B x D/8 pixel groups
-__global__ void deinterleave_persist_kernel(const float4* __restrict__ x, unsigned short* __restrict__ xp,
-                                            int B, int D, int ldx) {
-  const int nq = D / 8;
-  const size_t n = (size_t)B * nq;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    const int b = (int)(i / nq), q = (int)(i % nq);
-    const float4* src = x + ((size_t)b * 3 * D) / 4 + 6 * (size_t)q;
-    float4 v[6];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) v[k] = src[k];
-    deint_put<2>(v, nullptr, xp, B, b, (size_t)8 * q, ldx, 0);
-  }
-}
-
 __global__ void deinterleave_scalar_kernel(const float* __restrict__ x, float* __restrict__ xs,
                                            unsigned short* __restrict__ xp, int* __restrict__ dyn,
                                            int B, int D, int ldx, int f32mask, int* __restrict__ dyn_next) {
@@ -831,7 +816,7 @@ __global__ __launch_bounds__(256) void make_batch4_kernel(const unsigned char* _
 // The layer-0 pixel operand of a 0/1 batch as BitMats (deint_bits.h): one workgroup per task of
 // 64 batch rows x 64 PB pixels. Raises the not-binary word (*dyn slot 2) when a pixel is neither 0
 // nor 1: the step then runs deint_grey_kernel (the planes) and the GEMMs read the planes.
-template <int PB, int NT, int OS, bool NTL = false, bool NOW = false, bool CO = false>
+template <int PB, int NT, int OS, bool NOW = false>
 __global__ __launch_bounds__(NT) void deint_bits_kernel(const float4* __restrict__ x, int B, int D, int kts_f,
                                                         int kts_w, unsigned* __restrict__ xbf,
                                                         unsigned* __restrict__ xbw,
@@ -839,21 +824,14 @@ __global__ __launch_bounds__(NT) void deint_bits_kernel(const float4* __restrict
                                                         int* __restrict__ dyn, int* __restrict__ dyn_next) {
   if (dyn_next && (blockIdx.x | blockIdx.y | threadIdx.x) == 0) dyn_next[0] = dyn_next[2] = 0;
   __shared__ __attribute__((aligned(16))) DeintLds<PB, OS> bt;
-  if constexpr (CO) {
-    __shared__ __attribute__((aligned(16))) float4 stage[2][16][96];
-    deint_bits_task<PB, NT, OS, NTL, NOW, true>(x, B, D, kts_f, kts_w, xbf, xbw, xbits, ldbits, dyn, blockIdx.x,
-                                                blockIdx.y, bt, stage);
-  } else {
-    deint_bits_task<PB, NT, OS, NTL, NOW>(x, B, D, kts_f, kts_w, xbf, xbw, xbits, ldbits, dyn, blockIdx.x, blockIdx.y,
-                                          bt);
-  }
+  deint_bits_task<PB, NT, OS, NOW>(x, B, D, kts_f, kts_w, xbf, xbw, xbits, ldbits, dyn, blockIdx.x, blockIdx.y, bt);
 }
 
 // The weight gradient's BitMat (pixels x stacked rows) from the forward's (stacked rows x
 // pixels): one wave per 64 x 64 bit tile -- a quarter of a block on either side -- its 128 words in,
 // the tile as [8 pixel octets][64 rows] bytes in LDS, its 128 transposed words out (the 8 x 8 bit
-// transpose of deint_bits.h). The de-interleave then writes only the forward words (deint
-// variant 7): the transpose runs on the side stream beside the layer-0 forward, whose 192 tiles
+// transpose of deint_bits.h). The de-interleave then writes only the forward words
+// (launch_deint_bits with no_xbw): the transpose runs on the side stream beside the layer-0 forward, whose 192 tiles
 // (C3) leave CUs free, and the layer-0 weight gradient waits for it.
 __device__ __forceinline__ unsigned bits_compact(unsigned s) {  // inverse of bits_spread (low byte)
   unsigned e = s & 0xFu, o = (s >> 16) & 0xFu;
@@ -906,14 +884,9 @@ __global__ __launch_bounds__(256) void bits_transpose_kernel(const unsigned* __r
 // not-binary word; else every workgroup returns at once): bf16 plane 0 (planes 1-2 of the exact
 // split too when np == 3), the fp32 rows of the blocks in f32mask, and the inexact flag (*dyn) --
 // what the plane path's GEMMs and the BCE epilogue read. Workgroups stride over the 8-pixel groups.
-// done (the fused launch's chunk counters, DeintJob::done): zeroed for the next launch, whose
-// workers count from 0 (this kernel runs after every fused launch, in stream order)
 __global__ void deint_grey_kernel(const float4* __restrict__ x, float* __restrict__ xs,
                                   unsigned short* __restrict__ xp, long long ps, int np, int f32mask,
-                                  int* __restrict__ dyn, int B, int D, int ldx, int* __restrict__ done,
-                                  int ndone) {
-  if (done && blockIdx.x == 0)
-    for (int i = threadIdx.x; i < ndone; i += blockDim.x) done[i] = 0;
+                                  int* __restrict__ dyn, int B, int D, int ldx) {
   if (dyn[2] == 0) return;
   const int nq = D / 8;
   const size_t n = (size_t)B * nq;
@@ -964,59 +937,19 @@ hipError_t launch_deinterleave(const float* x, float* xs, const Planes& xp, int*
 
 hipError_t launch_deint_bits(const float* x, int B, int D, unsigned* xbf, int kts_f, unsigned* xbw, int kts_w,
                              unsigned char* xbits, int ldbits, int* dyn, int* dyn_next, float* xs,
-                             const Planes& xp, int ldx, int f32dyn_mask, hipStream_t st, int variant) {
+                             const Planes& xp, int ldx, int f32dyn_mask, bool no_xbw, hipStream_t st) {
   if ((D % 8) || (B % 64) || (reinterpret_cast<uintptr_t>(x) % 16) || (ldx % 8) || !dyn || !xp.p ||
       kts_f != bitmat_kts(D + 1) || kts_w != bitmat_kts(3 * B))
     return hipErrorInvalidValue;
   const float4* x4 = reinterpret_cast<const float4*>(x);
-  switch (variant) {  // (diagnostics: mvae_bench_deint) 0 = the step's form
-    case 5: {  // the fused launch's LDS-DMA workers alone, one per CU
-      DeintJob j;
-      j.x = x; j.B = B; j.D = D; j.kts_f = kts_f; j.kts_w = kts_w;
-      j.xbf = xbf; j.xbw = xbw; j.xbits = xbits; j.ldbits = ldbits; j.dyn = dyn; j.dyn_next = dyn_next;
-      j.nchunks = (kts_f + DEINT_FUSE_PB - 1) / DEINT_FUSE_PB;
-      j.nworkers = 256;
-      const hipError_t e = launch_deint_persist(j, st);
-      if (e != hipSuccess) return e;
-      break;
-    }
-    case 7:  // the step's form without the weight-gradient words (launch_bits_transpose writes them)
-      hipLaunchKernelGGL((deint_bits_kernel<2, 256, 72, false, true>), dim3((kts_f + 1) / 2, B / 64), dim3(256), 0, st,
-                         x4, B, D, kts_f, kts_w, xbf, xbw, xbits, ldbits, dyn, dyn_next);
-      break;
-    case 8:  // the step's form with coalesced loads of X through an LDS stage (deint_load_co)
-      hipLaunchKernelGGL((deint_bits_kernel<2, 256, 72, false, false, true>), dim3((kts_f + 1) / 2, B / 64), dim3(256), 0,
-                         st, x4, B, D, kts_f, kts_w, xbf, xbw, xbits, ldbits, dyn, dyn_next);
-      break;
-    case 9:  // variant 7 with coalesced loads
-      hipLaunchKernelGGL((deint_bits_kernel<2, 256, 72, false, true, true>), dim3((kts_f + 1) / 2, B / 64), dim3(256), 0,
-                         st, x4, B, D, kts_f, kts_w, xbf, xbw, xbits, ldbits, dyn, dyn_next);
-      break;
-    case 6:  // the step's form with non-temporal loads of X (2x slower: r6zb_deint_nt_loads.txt)
-      hipLaunchKernelGGL((deint_bits_kernel<2, 256, 72, true>), dim3((kts_f + 1) / 2, B / 64), dim3(256), 0, st, x4, B,
-                         D, kts_f, kts_w, xbf, xbw, xbits, ldbits, dyn, dyn_next);
-      break;
-    case 1:
-      hipLaunchKernelGGL((deint_bits_kernel<2, 256, 64>), dim3((kts_f + 1) / 2, B / 64), dim3(256), 0, st, x4, B, D,
-                         kts_f, kts_w, xbf, xbw, xbits, ldbits, dyn, dyn_next);
-      break;
-    case 2:
-      hipLaunchKernelGGL((deint_bits_kernel<4, 512, 72>), dim3((kts_f + 3) / 4, B / 64), dim3(512), 0, st, x4, B, D,
-                         kts_f, kts_w, xbf, xbw, xbits, ldbits, dyn, dyn_next);
-      break;
-    case 3:
-      hipLaunchKernelGGL((deint_bits_kernel<1, 256, 72>), dim3(kts_f, B / 64), dim3(256), 0, st, x4, B, D,
-                         kts_f, kts_w, xbf, xbw, xbits, ldbits, dyn, dyn_next);
-      break;
-    case 4:
-      hipLaunchKernelGGL((deint_bits_kernel<4, 256, 72>), dim3((kts_f + 3) / 4, B / 64), dim3(256), 0, st, x4, B, D,
-                         kts_f, kts_w, xbf, xbw, xbits, ldbits, dyn, dyn_next);
-      break;
-    default:
-      hipLaunchKernelGGL((deint_bits_kernel<2, 256, 72>), dim3((kts_f + 1) / 2, B / 64), dim3(256), 0, st, x4, B, D,
-                         kts_f, kts_w, xbf, xbw, xbits, ldbits, dyn, dyn_next);
-  }
-  return launch_deint_grey(x, B, D, dyn, xs, xp, ldx, f32dyn_mask, nullptr, 0, st);
+  const dim3 grid((kts_f + 1) / 2, B / 64);
+  if (no_xbw)  // without the weight-gradient words (launch_bits_transpose writes them)
+    hipLaunchKernelGGL((deint_bits_kernel<2, 256, 72, true>), grid, dim3(256), 0, st, x4, B, D, kts_f, kts_w, xbf, xbw,
+                       xbits, ldbits, dyn, dyn_next);
+  else
+    hipLaunchKernelGGL((deint_bits_kernel<2, 256, 72>), grid, dim3(256), 0, st, x4, B, D, kts_f, kts_w, xbf, xbw, xbits,
+                       ldbits, dyn, dyn_next);
+  return launch_deint_grey(x, B, D, dyn, xs, xp, ldx, f32dyn_mask, st);
 }
 
 hipError_t launch_bits_transpose(const unsigned* xbf, int kts_f, unsigned* xbw, int kts_w, int B, hipStream_t st) {
@@ -1029,24 +962,10 @@ hipError_t launch_bits_transpose(const unsigned* xbf, int kts_f, unsigned* xbw, 
 }
 
 hipError_t launch_deint_grey(const float* x, int B, int D, int* dyn, float* xs, const Planes& xp, int ldx,
-                             int f32dyn_mask, int* done, int ndone, hipStream_t st) {
+                             int f32dyn_mask, hipStream_t st) {
   // (256 workgroups striding: for a 0/1 batch every one returns at once, and fewer cost less)
   hipLaunchKernelGGL(deint_grey_kernel, dim3(256), dim3(256), 0, st, reinterpret_cast<const float4*>(x), xs,
-                     xp.p, xp.stride, xp.n, f32dyn_mask, dyn, B, D, ldx, done, ndone);
-  return hipGetLastError();
-}
-
-hipError_t launch_deinterleave_grid(const float* x, unsigned short* xp, int B, int D, int ldx, int grid,
-                                    hipStream_t st) {
-  if ((D % 8) || (ldx % 8) || (reinterpret_cast<uintptr_t>(x) % 16)) return hipErrorInvalidValue;
-  if (grid < 0) {
-    dim3 g(nblocks(D / 8, 256), B);
-    hipLaunchKernelGGL(deinterleave_vecn_kernel<2>, g, dim3(256), 0, st, reinterpret_cast<const float4*>(x),
-                       nullptr, xp, nullptr, B, D, ldx, 0, nullptr, nullptr, 0);
-  } else if (grid > 0) {
-    hipLaunchKernelGGL(deinterleave_persist_kernel, dim3(grid), dim3(256), 0, st,
-                       reinterpret_cast<const float4*>(x), xp, B, D, ldx);
-  }
+                     xp.p, xp.stride, xp.n, f32dyn_mask, dyn, B, D, ldx);
   return hipGetLastError();
 }
 

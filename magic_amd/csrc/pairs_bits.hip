@@ -107,8 +107,8 @@ __global__ __launch_bounds__(256) void pairs_bits_kernel(const unsigned char* __
     nb |= deint_octet_put<PB, OS>(in, pad, e, xbits + (size_t)(b0 + r) * ldbits + (pix >> 3), bt, o, r);
   }
   auto none = [] {};
-  deint_tail<PB, NT, OS, false, decltype(none)&, decltype(none)&, NOW>(nb, B, D, kts_f, kts_w, xbf, xbw, dyn, bx, by,
-                                                                       bt, none, none);
+  deint_tail<PB, NT, OS, decltype(none)&, decltype(none)&, NOW>(nb, B, D, kts_f, kts_w, xbf, xbw, dyn, bx, by, bt,
+                                                                none, none);
 }
 
 // deint_grey_kernel's pass (only after pairs_bits_kernel raised the not-binary word; else every

@@ -56,6 +56,31 @@ def test_create_rejects_bad_config_without_gpu_work():
     assert lib.mvae_create(None, 0, ctypes.byref(h)) < 0
 
 
+REMOVED_OPTIONS = ["deint_fuse=1", "deint_fuse_diag=1", "deint_variant=8", "e8_prio=1", "diag_skip_deint=1",
+                   "diag_shadow_deint=1", "diag_shadow_at=1", "diag_chain=1"]
+
+
+@pytest.mark.parametrize("option", REMOVED_OPTIONS)
+def test_create_rejects_removed_options(option):
+    """The rejected experiments' create options are gone: each name is an unknown option now
+    (MVAE_EINVAL, a null handle). Options are parsed before the first HIP call, so no GPU is needed."""
+    lib = _lib.load()
+    c = _lib.mvae_cfg()
+    c.image_size, c.batch, c.global_batch = 10, 4, 4
+    c.n_enc = 2
+    c.enc[0], c.enc[1] = 12, 10
+    c.dec[0], c.dec[1] = 10, 12
+    c.latent = 3
+    c.deform_weight = 1.0
+    c.lr[0], c.lr[1] = 1e-3, 1e-3
+    c.beta1, c.beta2, c.epsilon = 0.9, 0.999, 1e-8
+    h = ctypes.c_void_p()
+    rc = lib.mvae_create_ex(ctypes.byref(c), 0, option.encode(), ctypes.byref(h))
+    assert rc == -1 and h.value is None  # MVAE_EINVAL
+    err = lib.mvae_last_error(None)
+    assert b"unknown option" in err and option.encode() in err, err
+
+
 def test_engine_fails_loudly_without_gpu():
     import torch
     if torch.cuda.is_available():

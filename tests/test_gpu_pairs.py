@@ -210,7 +210,6 @@ MATERIALISING = {
     "conv": dict(conv=True, image_size=8, batch=64),
     "bits0": dict(options="bits=0"),
     "e8_0": dict(options="e8=0"),
-    "deint_fuse": dict(options="deint_fuse=1"),
 }
 
 

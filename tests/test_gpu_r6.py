@@ -35,8 +35,8 @@ def test_gemm_bits_path_bitwise_equal_planes(reg, prec, at, epi, M, N, K):
     """variant 13 forces the eight-phase kernel; epi bit 14 hands it A as a BitMat too: the bits
     path must reproduce the plane path bit for bit in bf16, to fp32 rounding in f32x (ragged M / N /
     K, partial k-tiles, split-K at K 4099 / 10001, one-block shapes), and float64 at the bars.
-    reg (epi bit 15): the words loaded to registers by each wave (the fused de-interleave's form)
-    instead of through an LDS copy of the block."""
+    reg (epi bit 15): the words loaded to registers by each wave (the step's default form) instead of
+    through an LDS copy of the block."""
     lib = _lib.load()
     g = torch.Generator(device="cuda").manual_seed(M * 3 + N * 7 + K + 11 * at + epi)
     A = _bin(K, M, g) if at else _bin(M, K, g)
@@ -73,102 +73,18 @@ def test_gemm_bits_grey_operand_takes_plane_path():
     assert torch.equal(Cb[:, :N], Cp[:, :N])
 
 
-# ------------------------------------------------------------------ the fused de-interleave
+# ------------------------------------------------------------------ batches of the step tests
 
 def _batches(cfg, n, grey_at, seed):
     g = torch.Generator(device="cuda").manual_seed(seed)
     out = []
     for i in range(n):
         x = (torch.rand(cfg.batch, 3 * cfg.D, device="cuda", generator=g) < 0.1).float()
-        if i == grey_at:  # a batch with pixels other than 0 / 1: the grey pass + plane-path fallback
+        if i == grey_at:  # a batch with pixels other than 0 / 1: the grey pass + the plane path
             x = x * torch.randint(1, 256, x.shape, device="cuda", generator=g).float() / 255.0
         a = torch.randint(296, 6427, (cfg.batch,), device="cuda", generator=g).float()
         out.append((x, a))
     return out
-
-
-def test_deint_fuse_c3_steps_bitwise():
-    """C3 (bf16, B = 8192, 100x100, L = 200): the de-interleave's workers inside the layer-0
-    forward's launch (create option deint_fuse; 192 tiles + 64 workers, the tiles polling the
-    workers' chunk counters) against the separate de-interleave launch -- the same forward split
-    (1), so three training steps (the second batch grey: the plane-path fallback) leave bitwise
-    identical parameters and losses."""
-    from magic_amd.config import baseline_config
-    from magic_amd.engine import Engine
-    from tests.gpu_helpers import make_params
-    cfg = baseline_config("C3")
-    assert cfg.precision == "bf16" and cfg.batch == 8192
-    P = make_params(cfg)
-    batches = _batches(cfg, 3, 1, 7)
-    res = []
-    for fuse in (0, 1):
-        eng = Engine(cfg.replace(options=f"deint_fuse={fuse}"), 0)
-        try:
-            eng.load_params(P)
-            L = []
-            for x, a in batches:
-                eng.train_step(x, a)
-                L.append(eng.losses.clone())
-            torch.cuda.synchronize()
-            res.append(({k: v.cpu() for k, v in eng.params().items()}, torch.stack(L).cpu()))
-        finally:
-            eng.close()
-    (p0, l0), (p1, l1) = res
-    assert torch.equal(l0, l1), (l0, l1)
-    for k in p0:
-        assert torch.equal(p0[k], p1[k]), k
-
-
-def test_deint_fuse_c2_gradients_match():
-    """C2 (f32x, B = 4096): the fused launch runs the forward at split 2 (96 tiles x 2 + 64
-    workers), the separate path at the planner's split: the same products summed in another order,
-    so one binary and one grey batch's losses and gradients agree to fp32 rounding."""
-    from magic_amd.config import baseline_config
-    from magic_amd.engine import Engine
-    from tests.gpu_helpers import make_params
-    cfg = baseline_config("C2")
-    assert cfg.precision == "f32x"
-    P = make_params(cfg)
-    batches = _batches(cfg, 2, 1, 9)
-    res = []
-    for fuse in (0, 1):
-        eng = Engine(cfg.replace(options=f"deint_fuse={fuse}"), 0)
-        try:
-            eng.load_params(P)
-            r = []
-            for x, a in batches:
-                eng.forward(x)
-                eng.metric(a)
-                eng.backward()
-                torch.cuda.synchronize()
-                r.append((eng.losses.cpu().double(),
-                          {k: v.cpu().double() for k, v in eng.tensors(_lib.KIND_GRAD1).items()},
-                          {k: v.cpu().double() for k, v in eng.tensors(_lib.KIND_GRAD2).items()}))
-            res.append(r)
-        finally:
-            eng.close()
-    for (l0, g10, g20), (l1, g11, g21) in zip(*res):
-        assert ((l0 - l1).abs() <= 1e-5 * l0.abs().clamp_min(1e-3)).all(), (l0, l1)
-        for g0, g1 in ((g10, g11), (g20, g21)):
-            for k in g0:
-                scale = g0[k].abs().max().clamp_min(1e-30)
-                assert (g0[k] - g1[k]).abs().max() / scale <= 1e-4, k
-
-
-@pytest.mark.parametrize("prec", ["f32x", "bf16"])
-@pytest.mark.parametrize("grey", [False, True], ids=["binary", "grey"])
-def test_deint_fuse_small_step_vs_oracle(prec, grey):
-    """The fused launch at a small ragged shape (20x20 images, B = 320, 300/260/280-wide encoder:
-    8 tiles + 248 workers, more workers than tasks, a partial last chunk) against the float64
-    oracle at the bars of test_step_wide_kernels."""
-    from magic_amd.config import preset
-    from tests.test_gpu_parity import check_step
-    cfg = preset("8c", image_size=20, batch=320, precision=prec).replace(enc=(300, 260, 280),
-                                                                       options="deint_fuse=1")
-    if prec == "f32x":
-        check_step(cfg, grey=grey, recon=True)
-    else:
-        check_step(cfg, grey=grey, tol=5e-2, loss_tol=2e-3, dist_tol=2e-2, recon=True)
 
 
 # ------------------------------------------------------------------ xbw transposed from xbf
@@ -232,18 +148,3 @@ def test_cs_one_steps_bitwise(case):
     assert cfg.metric == "cosine"
     _steps_bitwise(cfg, "cs_one=0", "cs_one=1")  # (forced on: the default is on only where L <= 32)
 
-
-# ------------------------------------------------------------------ coalesced de-interleave loads
-
-@pytest.mark.parametrize("case", ["C3", "C2", "small"])
-def test_deint_coalesced_steps_bitwise(case):
-    """deint_variant 8: the de-interleave's X loads coalesced through an LDS stage (deint_load_co)
-    -- the same BitMats, target bits and not-binary word, so three steps (the second batch grey)
-    are bitwise the default's; C3 takes its weight-gradient-words-free form (xbw_split), C2 the
-    whole form, and the small shape (D = 400) a partial last pixel task."""
-    from magic_amd.config import baseline_config, preset
-    if case == "small":
-        cfg = preset("8c", image_size=20, batch=320, precision="bf16").replace(enc=(300, 260, 280))
-    else:
-        cfg = baseline_config(case)
-    _steps_bitwise(cfg, "", "deint_variant=8")

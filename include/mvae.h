@@ -385,6 +385,32 @@ int mvae_pair_scores(mvae_ctx* ctx, const float* zl, const float* zk, int64_t n,
 int mvae_match_merge(mvae_ctx* ctx, const float* vals, const int* idx, int64_t N, int parts, int k, int order,
                      float* top_val, int* top_idx, void* stream);
 
+/* ---- maximum overlap of a lock and a key: the label the distance is trained on -------------
+ * Additive to ABI 7 (the loader's build id rejects a stale library).
+ *   foreground   a table byte >= 128: Lb of the lock, Kb of the key
+ *   Kr_r         Kb rotated by coef[r] = (cos, sin, x_off, y_off) exactly as mvae_make_batch rotates
+ *                the lock (output (x, y) samples ((c x - s y) + x_off, (s x + c y) + y_off) in
+ *                unfused fp32, roundf, zero fill)
+ *   ov(r, dy, dx) = sum_{y,x} Lb[y, x] Kr_r[y - dy, x - dx],  |dy| <= H - 1, |dx| <= W - 1
+ *   area = max ov;  pose = the lexicographically smallest (r, dy, dx) reaching it; (0, 0, 0) when
+ *   the area is 0. Integer work: the result is exact.
+ * Maximum overlap of lock lock_idx[i] and key key_idx[i], i < count.
+ * locks, keys: device uint8 [n][H][W]; lock_idx / key_idx: device int32 [count] (NULL: i), not
+ * checked, as for mvae_make_batch; coef: device float [n_rot][4], 16-byte aligned, shared by all
+ * pairs; area_out: device int32 [count]; pose_out: device int32 [count][3] or NULL;
+ * work: device buffer of mvae_overlap_work_bytes(...) bytes, 8-byte aligned (NULL allowed if that
+ * is 0), one 8-byte partial per pair and chunk of angles: its contents need not survive the call.
+ * Context-free, allocates nothing, enqueues on `stream`, like mvae_make_batch.
+ * MVAE_EINVAL with a message (mvae_last_error(NULL)) beginning "mvae_overlap_pairs", before any
+ * launch: a null table, coef or area_out, count < 1, n_rot outside 1 .. 2^24, height or width
+ * outside 1 .. 256, a misaligned coef or work, work null while bytes are needed.
+ * mvae_overlap_work_bytes returns 0 for arguments mvae_overlap_pairs refuses. */
+size_t mvae_overlap_work_bytes(int64_t count, int n_rot, int height, int width);
+int mvae_overlap_pairs(const unsigned char* locks, const unsigned char* keys, int height, int width,
+                       const int* lock_idx, const int* key_idx, int64_t count,
+                       const float* coef, int n_rot, int* area_out, int* pose_out,
+                       void* work, void* stream);
+
 /* ---- diagnostics ------------------------------------------------------------------ */
 /* HIP-event timing of named regions (one GEMM incl. its split-K reduction, or one
  * bandwidth kernel group), recorded on the launch stream while enabled.               */

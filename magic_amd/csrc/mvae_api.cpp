@@ -2570,6 +2570,34 @@ extern "C" int mvae_make_batch(const unsigned char* locks, const unsigned char* 
   return MVAE_OK;
 }
 
+extern "C" size_t mvae_overlap_work_bytes(int64_t count, int n_rot, int height, int width) {
+  if (count < 1 || n_rot < 1 || n_rot > OVERLAP_MAX_ROT || height < 1 || height > 256 || width < 1 || width > 256)
+    return 0;  // mvae_overlap_pairs refuses these arguments
+  return overlap_work_bytes(count, n_rot);
+}
+
+extern "C" int mvae_overlap_pairs(const unsigned char* locks, const unsigned char* keys, int height, int width,
+                                  const int* lock_idx, const int* key_idx, int64_t count, const float* coef,
+                                  int n_rot, int* area_out, int* pose_out, void* work, void* stream) {
+  if (!locks || !keys || !coef || !area_out)
+    return fail(nullptr, MVAE_EINVAL, "mvae_overlap_pairs: null locks, keys, coef or area_out");
+  if (count < 1) return fail(nullptr, MVAE_EINVAL, "mvae_overlap_pairs: count must be at least 1");
+  if (n_rot < 1 || n_rot > OVERLAP_MAX_ROT)
+    return fail(nullptr, MVAE_EINVAL, "mvae_overlap_pairs: n_rot must be in [1, 16777216]");
+  if (height < 1 || height > 256 || width < 1 || width > 256)
+    return fail(nullptr, MVAE_EINVAL, "mvae_overlap_pairs: height and width must be in [1, 256]");
+  if ((reinterpret_cast<uintptr_t>(coef) & 15) != 0)
+    return fail(nullptr, MVAE_EINVAL, "mvae_overlap_pairs: coef must be 16-byte aligned");
+  if (!work && overlap_work_bytes(count, n_rot) != 0)
+    return fail(nullptr, MVAE_EINVAL, "mvae_overlap_pairs: work is null but mvae_overlap_work_bytes is not 0");
+  if ((reinterpret_cast<uintptr_t>(work) & 7) != 0)
+    return fail(nullptr, MVAE_EINVAL, "mvae_overlap_pairs: work must be 8-byte aligned");
+  hipError_t e = launch_overlap_pairs(locks, keys, height, width, lock_idx, key_idx, count, coef, n_rot, area_out,
+                                      pose_out, work, (hipStream_t)stream);
+  if (e != hipSuccess) { g_create_err = hipGetErrorString(e); return (int)e; }
+  return MVAE_OK;
+}
+
 // One conv2 kernel of the conv tower on caller data (tests only; synchronous): S1 x S1 x 64
 // images, B = batch (3B forward images, 4B backward images). mode 0: out = relu(conv(x, W) + b)
 // over 3B images (y = W2 block [1601][64]); mode 1: out = data gradient conv(x, W rotated) over

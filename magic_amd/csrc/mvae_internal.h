@@ -303,6 +303,16 @@ hipError_t launch_rnorm(const double* colsq, int L, float* r, hipStream_t st);
 // out[i] = the score of lock row i and key row i, in match_kernel's operations
 hipError_t launch_pair_scores(const float* zl, const float* zk, long long n, int L, int metric, int recip,
                               const float* rl, const float* rk, float* out, hipStream_t st);
+// ---- maximum overlap of lock / key pairs over rotations and shifts (overlap.hip) ----
+// area_out[i] = max over r < n_rot, dy, dx of |lock lock_idx[i] & shift(rotate(key key_idx[i], coef[r]),
+// dy, dx)|, pose_out[i] (or null) its smallest (r, dy, dx); null index lists: i. H, W in 1 .. 256,
+// n_rot in 1 .. OVERLAP_MAX_ROT, work of overlap_work_bytes bytes (hipErrorInvalidValue otherwise,
+// before anything is launched).
+constexpr int OVERLAP_MAX_ROT = 1 << 24;
+size_t overlap_work_bytes(long long count, int n_rot);
+hipError_t launch_overlap_pairs(const unsigned char* locks, const unsigned char* keys, int H, int W,
+                                const int* lock_idx, const int* key_idx, long long count, const float* coef,
+                                int n_rot, int* area_out, int* pose_out, void* work, hipStream_t st);
 // ---- conv-encoder tower (conv_tower.hip, conv_mfma.hip) ----
 // NHWC fp32 activations of the stacked batch (3B forward rows, 4B backward rows); S = image
 // side, S1 = S/2 (after pool 1), S2 = S/4 (after pool 2).

@@ -130,13 +130,20 @@ def main(argv=None):
                          "(a gallery larger than the device)")
     ap.add_argument("--retrieve-ranks", action="store_true",
                     help="with --retrieve: also the rank of key i for lock i -- MRR and median rank")
+    ap.add_argument("--labels", choices=("sampled", "computed"), default="sampled",
+                    help="sampled: the source's areas, or for synthetic shapes draws from the reference's "
+                         "recorded areas (unrelated to the images); computed: the maximum overlap of each "
+                         "lock / key pair of the pool, computed on the GPU before training")
+    ap.add_argument("--label-angles", type=int, default=360, metavar="R",
+                    help="with --labels computed: the key is tried at R equally spaced rotations")
     args = ap.parse_args(argv)
     cfg = preset(args.preset, image_size=args.image_size, batch=args.batch or None)
     eight_c = args.preset in ("8c", "8d", "8e", "8f")
     driver = args.driver or ("8c" if eight_c else "11a")
     vae = TangoEncoder(None, config=cfg, compat="8c" if eight_c else "11a")
     batches = overlap_input.inputs(normalize=True, reshape=True, rotation=True, batch_size=cfg.batch,
-                                   image_size=cfg.image_size, data_dir=args.data, fused=args.fused_input)
+                                   image_size=cfg.image_size, data_dir=args.data, fused=args.fused_input,
+                                   labels=args.labels, label_angles=args.label_angles)
     t0 = time.time()
     train(vae, batches, max(args.samples_per_epoch, cfg.batch), args.epochs, driver=driver)
     print(f"done in {time.time() - t0:.1f}s", file=sys.stderr)

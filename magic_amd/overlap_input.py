@@ -62,6 +62,61 @@ def make_batch(locks: torch.Tensor, keys: torch.Tensor, idx: torch.Tensor, coef:
     return out
 
 
+def angle_coefficients(angles, height: int, width: int) -> np.ndarray:
+    """The rotations ``max_overlap`` searches: an int R means the angles ``2 pi r / R`` (float64, cast
+    to fp32), anything else an array of radians; through ``rotation_coefficients`` -> [n_rot, 4]."""
+    if isinstance(angles, (int, np.integer)):
+        if angles < 1:
+            raise ValueError("max_overlap: at least one angle expected")
+        angles = (2.0 * np.pi * np.arange(int(angles), dtype=np.float64) / int(angles)).astype(np.float32)
+    a = np.asarray(angles, np.float32).reshape(-1)
+    if a.size < 1:
+        raise ValueError("max_overlap: at least one angle expected")
+    return rotation_coefficients(a, height, width)
+
+
+def max_overlap(locks: torch.Tensor, keys: torch.Tensor, lock_idx: Optional[torch.Tensor] = None,
+                key_idx: Optional[torch.Tensor] = None, angles=360) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The label the distance is trained on, computed (``mvae_overlap_pairs``): for pair ``i`` of
+    lock ``lock_idx[i]`` and key ``key_idx[i]`` (``None``: ``i``), the largest number of foreground
+    pixels (byte >= 128) the lock shares with the key rotated by one of ``angles`` (the batch
+    producer's nearest-neighbour rotation) and shifted by whole pixels. uint8 device tables
+    [n, H, W] and [m, H, W], int32 device index lists [count] -> (areas int32 [count], pose int32
+    [count, 3] = the smallest (angle index, dy, dx) reaching the area; (0, 0, 0) for area 0)."""
+    from . import _lib
+    lib = _lib.load()
+    for t in (locks, keys):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.uint8 or not t.is_contiguous() \
+                or t.dim() != 3:
+            raise ValueError("max_overlap: contiguous uint8 device tables [n, H, W] expected")
+    if keys.shape[1:] != locks.shape[1:] or keys.device != locks.device:
+        raise ValueError("max_overlap: the tables must share H, W and the device")
+    for t in (lock_idx, key_idx):
+        if t is not None and (not t.is_cuda or t.dtype != torch.int32 or not t.is_contiguous() or t.dim() != 1):
+            raise ValueError("max_overlap: int32 device index lists [count] expected")
+    if lock_idx is not None and key_idx is not None and lock_idx.shape != key_idx.shape:
+        raise ValueError("max_overlap: lock_idx and key_idx must have one length")
+    given = lock_idx if lock_idx is not None else key_idx
+    count = given.shape[0] if given is not None else min(locks.shape[0], keys.shape[0])
+    if (lock_idx is None and count > locks.shape[0]) or (key_idx is None and count > keys.shape[0]):
+        raise ValueError("max_overlap: more pairs than images in the table without an index list")
+    h, w = int(locks.shape[1]), int(locks.shape[2])
+    dev = locks.device
+    coef = torch.from_numpy(angle_coefficients(angles, h, w)).to(dev)
+    n_rot = coef.shape[0]
+    areas = torch.empty(count, dtype=torch.int32, device=dev)
+    pose = torch.empty(count, 3, dtype=torch.int32, device=dev)
+    nbytes = lib.mvae_overlap_work_bytes(count, n_rot, h, w)
+    work = torch.empty(max(nbytes // 8, 1), dtype=torch.int64, device=dev)
+    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    with torch.cuda.device(dev):
+        rc = lib.mvae_overlap_pairs(locks.data_ptr(), keys.data_ptr(), h, w, ptr(lock_idx), ptr(key_idx), count,
+                                    coef.data_ptr(), n_rot, areas.data_ptr(), pose.data_ptr(), work.data_ptr(),
+                                    torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(lib, None, rc)
+    return areas, pose
+
+
 class PairBatch:
     """One batch described by its sources instead of materialised: the uint8 device tables
     ``locks`` / ``keys`` [n, H, W], the example ``idx`` int32 [B] of each row and its rotation
@@ -132,9 +187,19 @@ def area_distribution() -> np.ndarray:
     return np.clip(np.exp(rng.normal(7.4, 0.62, 2000)), 296, 6426).round().astype(np.float32)
 
 
+def _check_labels(labels: str) -> bool:
+    if labels not in ("sampled", "computed"):
+        raise ValueError(f"labels must be 'sampled' or 'computed', not {labels!r}")
+    return labels == "computed"
+
+
 def synthetic_batch(batch: int, image_size: int, seed: int = 1, device="cuda",
-                    dtype=torch.float32) -> Tuple[torch.Tensor, torch.Tensor]:
-    """One seeded synthetic batch (X [B, 3D] in {0,1}, areas [B]) through the HIP producer."""
+                    dtype=torch.float32, labels: str = "sampled",
+                    label_angles=360) -> Tuple[torch.Tensor, torch.Tensor]:
+    """One seeded synthetic batch (X [B, 3D] in {0,1}, areas [B]) through the HIP producer.
+    ``labels="computed"``: the areas are ``max_overlap`` of each row's lock and key over
+    ``label_angles`` instead of draws from the reference's recorded areas."""
+    computed = _check_labels(labels)
     gen = torch.Generator().manual_seed(seed)
     dev = torch.device(device)
     lock = (random_shapes(batch, image_size, gen, device) * 255).to(torch.uint8).contiguous()
@@ -146,6 +211,8 @@ def synthetic_batch(batch: int, image_size: int, seed: int = 1, device="cuda",
     dist = area_distribution()
     sel = torch.randint(0, len(dist), (batch,), generator=gen).numpy()
     areas = torch.from_numpy(dist[sel]).to(dev)
+    if computed:
+        areas = max_overlap(lock, key, angles=label_angles)[0].float()
     return x, areas
 
 
@@ -200,11 +267,16 @@ class BatchStream:
     """Shuffled epochs over a source (``slice_input_producer(shuffle=True)`` +
     ``shuffle_batch``), a uniform [0, 2pi) rotation per example, /255 normalisation — the
     per-batch assembly runs in the HIP batch producer (``mvae_make_batch``). ``fused=True``: the
-    same draws yield ``(PairBatch, areas)`` and launch nothing; the step reads the tables."""
+    same draws yield ``(PairBatch, areas)`` and launch nothing; the step reads the tables.
+    ``labels="sampled"`` (default): the areas are the source's, or for the synthetic pool draws from
+    the reference's recorded areas, unrelated to the images. ``labels="computed"``: the area of pair
+    ``i`` of the pool is ``max_overlap`` of its lock and key over ``label_angles``, computed once here."""
 
     def __init__(self, batch: int, image_size: int, source: Optional[PairSource] = None,
                  normalize: bool = True, seed: int = 1, device="cuda", synthetic_pool: int = 960,
-                 reshape: bool = True, fp16: bool = False, fused: bool = False):
+                 reshape: bool = True, fp16: bool = False, fused: bool = False, labels: str = "sampled",
+                 label_angles=360):
+        computed = _check_labels(labels)
         if fused and (not reshape or fp16):
             raise ValueError("fused=True yields a PairBatch, not an array: reshape=False and USE_FP16 "
                              "ask for the array")
@@ -228,6 +300,8 @@ class BatchStream:
         self.locks = locks.round().clamp(0, 255).to(torch.uint8).contiguous().to(self.device)
         self.keys = keys.round().clamp(0, 255).to(torch.uint8).contiguous().to(self.device)
         self.areas = self.areas.float().to(self.device)
+        if computed:
+            self.areas = max_overlap(self.locks, self.keys, angles=label_angles)[0].float()
         self._perm = np.empty(0, dtype=np.int64)
         self._pos = 0
 
@@ -265,12 +339,12 @@ class BatchStream:
 def inputs(normalize: bool = False, reshape: bool = False, rotation: bool = False,
            batch_size: Optional[int] = None, image_size: Optional[int] = None,
            data_dir: Optional[str] = None, device="cuda", seed: int = 1,
-           fused: bool = False) -> BatchStream:
+           fused: bool = False, labels: str = "sampled", label_angles=360) -> BatchStream:
     """``11a/overlap_input.py:76-122``: images [B, H*W*3] (``reshape=True``) or [B, H, W, 3],
     divided by 255 when ``normalize``, cast to float16 with labels when ``FLAGS.USE_FP16``;
     ``rotation=False`` raises as in the reference (``:95-96``). ``fused=True`` (needs
     ``reshape=True`` and no ``USE_FP16``): images are ``PairBatch`` descriptions of the same
-    batches, which ``TangoEncoder`` takes as X."""
+    batches, which ``TangoEncoder`` takes as X. ``labels`` / ``label_angles``: see ``BatchStream``."""
     if not rotation:
         raise ValueError("Rotation has to be True.")
     size = image_size or FLAGS.IMAGE_SIZE
@@ -281,4 +355,5 @@ def inputs(normalize: bool = False, reshape: bool = False, rotation: bool = Fals
         lim = FLAGS.NUM_EXAMPLES_TO_LOAD_INTO_QUEUE
         src = PairSource.from_packed(d, limit=lim) if d.endswith(".npz") else PairSource(d, limit=lim)
     return BatchStream(bs, size, src, normalize=normalize, seed=seed, device=device, reshape=reshape,
-                       fp16=bool(getattr(FLAGS, "USE_FP16", False)), fused=fused)
+                       fp16=bool(getattr(FLAGS, "USE_FP16", False)), fused=fused, labels=labels,
+                       label_angles=label_angles)

@@ -23,6 +23,8 @@ class Retrieval(NamedTuple):
     ranks: Optional[np.ndarray] = None   # [min(n, m)] keys ahead of key i for lock i (0: it is the best)
     mrr: Optional[float] = None          # mean of 1 / (ranks + 1)
     median_rank: Optional[float] = None  # median of ranks + 1
+    true_hit_at_1: Optional[float] = None  # share of locks whose truly best key (``truth``) comes first
+    true_hit_at_k: Optional[float] = None  # ... or is among the k returned
 
 
 def _sharded(vae, locks, keys, k, order, normalize, return_dist, shard, ranks):
@@ -68,8 +70,28 @@ def _sharded(vae, locks, keys, k, order, normalize, return_dist, shard, ranks):
     return out + ((ahead[:nn].cpu().numpy(),) if ranks else ())
 
 
+def overlap_matrix(locks, keys, angles=360, chunk: int = 1 << 16) -> np.ndarray:
+    """The true label of every pair: ``[n, m]`` int32, entry (i, j) = ``max_overlap`` of lock ``i``
+    and key ``j`` over ``angles``. uint8 tables ``[n, H, W]`` and ``[m, H, W]`` (arrays or device
+    tensors); the index lists of at most ``chunk`` pairs at a time are built on the device."""
+    from .overlap_input import max_overlap
+    dev = locks.device if isinstance(locks, torch.Tensor) and locks.is_cuda else torch.device("cuda")
+    up = lambda t: torch.as_tensor(t).to(dev).contiguous()  # noqa: E731
+    locks, keys = up(locks), up(keys)
+    n, m = len(locks), len(keys)
+    if chunk < 1:
+        raise ValueError("overlap_matrix: chunk must be at least 1")
+    out = torch.empty(n * m, dtype=torch.int32, device=dev)
+    for p0 in range(0, n * m, chunk):
+        p = torch.arange(p0, min(p0 + chunk, n * m), device=dev, dtype=torch.int64)
+        li = torch.div(p, m, rounding_mode="floor").to(torch.int32)
+        ki = (p % m).to(torch.int32)
+        out[p0:p0 + len(p)] = max_overlap(locks, keys, li, ki, angles=angles)[0]
+    return out.view(n, m).cpu().numpy()
+
+
 def retrieve(vae, locks, keys, k: int = 10, order: int = 1, normalize: bool = True,
-             return_dist: bool = False, shard: Optional[int] = None, ranks: bool = False):
+             return_dist: bool = False, shard: Optional[int] = None, ranks: bool = False, truth=None):
     """``locks``, ``keys``: uint8 tables ``[n, S, S]`` and ``[m, S, S]`` (arrays or device tensors).
     Returns a ``Retrieval`` (and the ``[n, m]`` score matrix when ``return_dist``). The distance is
     trained to equal the overlap area, so the default ``order`` +1 ranks the largest predicted
@@ -81,7 +103,14 @@ def retrieve(vae, locks, keys, k: int = 10, order: int = 1, normalize: bool = Tr
     (for a cosine preset bit for bit when ``shard`` is a multiple of 256, else to the rounding of
     the fp64 column sums). ``ranks``: also, for each lock ``i < m``, how many keys rank before key
     ``i`` (``Retrieval.ranks``, 0 = best), counted in the scoring pass without the score matrix,
-    with ``mrr`` and ``median_rank`` (1-based) of them."""
+    with ``mrr`` and ``median_rank`` (1-based) of them. ``truth``: an ``[n, m]`` matrix of true labels
+    (``overlap_matrix``); ``true_hit_at_1`` / ``true_hit_at_k`` are then the share of locks whose
+    truly best key (the largest entry of its row, the smallest index on ties) is the first / among the
+    ``k`` returned."""
+    if truth is not None:
+        truth = truth.cpu().numpy() if isinstance(truth, torch.Tensor) else np.asarray(truth)
+        if truth.shape != (len(locks), len(keys)):
+            raise ValueError(f"retrieve: truth must be [{len(locks)}, {len(keys)}], not {list(truth.shape)}")
     if shard is not None or ranks:
         out = _sharded(vae, locks, keys, k, order, normalize, return_dist, shard, ranks)
     else:
@@ -92,10 +121,13 @@ def retrieve(vae, locks, keys, k: int = 10, order: int = 1, normalize: bool = Tr
     own = np.arange(n)[:, None]
     hit1 = float((ind[:n, :1] == own).any(1).mean())
     hitk = float((ind[:n] == own).any(1).mean())
-    extra = ()
+    extra = (None, None, None)
     if ranks:
         r = out[-1].astype(np.int64)
         extra = (r, float((1.0 / (r + 1)).mean()), float(np.median(r + 1)))
+    if truth is not None:
+        best = np.argmax(truth, axis=1)[:, None]  # the first maximum of a row
+        extra += (float((ind[:, :1] == best).any(1).mean()), float((ind == best).any(1).mean()))
     res = Retrieval(val, ind, hit1, hitk, k, order, *extra)
     return (res, out[2]) if return_dist else res
 
@@ -112,4 +144,6 @@ def report(r: Retrieval) -> str:
          f"({'largest' if r.order > 0 else 'smallest'} distance first)")
     if r.ranks is not None:
         s += f", MRR = {r.mrr:.4f}, median rank = {r.median_rank:g} over {len(r.ranks)} locks"
+    if r.true_hit_at_1 is not None:
+        s += f"; truly best key: hit@1 = {r.true_hit_at_1:.4f}, hit@{r.k} = {r.true_hit_at_k:.4f}"
     return s

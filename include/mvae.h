@@ -273,6 +273,40 @@ int mvae_transform_pairs(mvae_ctx* ctx, const mvae_pairs* pairs, float* zmean_ou
 int mvae_reconstruct_pairs(mvae_ctx* ctx, const mvae_pairs* pairs, const float* eps, float* y_out,
                            void* stream);
 
+/* ---- any lock with any key: a key index of its own ----------------------------------- */
+/* Additive to ABI 7 (the loader's build id rejects a stale library). Row b of a cross-pair batch is
+ * lock p.idx[b], the rotation of that lock, and key key_idx[b]: the label of such a row is the
+ * maximum overlap of that pair (mvae_overlap_pairs). The two tables may hold different numbers of
+ * images, n locks and m keys of one height and width; the descriptor carries neither count and the
+ * index ranges are the caller's precondition, as for mvae_make_batch (not checked: the kernels
+ * index the tables with them). */
+typedef struct mvae_xpairs {
+  mvae_pairs p;        /* p.idx[b]: the lock (and rotated lock) of row b, in [0, n)            */
+  const int* key_idx;  /* device int32 [B]: the key of row b, in [0, m); NULL: p.idx           */
+} mvae_xpairs;         /* LP64: 56 bytes, key_idx at offset 48 */
+/* mvae_make_batch with the key of row b taken from keys[key_idx[b]]; key_idx NULL or equal to
+ * lock_idx gives the bits of mvae_make_batch. MVAE_EINVAL with a message beginning
+ * "mvae_make_batch_x" for a null table, lock_idx, coef or x_out, a height, width or batch < 1, a
+ * divisor <= 0 or a coef that is not 16-byte aligned. */
+int mvae_make_batch_x(const unsigned char* locks, const unsigned char* keys, int height, int width,
+                      const int* lock_idx, const int* key_idx, const float* coef, int batch,
+                      float divisor, float* x_out, void* stream);
+/* The twins of the *_pairs entry points, under their contract: results are bitwise those of
+ * mvae_make_batch_x into an x followed by the x call, in every configuration. The direct kernel is
+ * taken exactly where *_pairs takes it (the same conditions, timing region "pairs_bits": the same
+ * kernels, which read the key's index from key_idx); everything else materialises into the
+ * context's lazy [B, 3 D] scratch (region "pairs_make_batch"). Validation is that of *_pairs on
+ * xpairs->p, the messages beginning with the entry point's name. */
+int mvae_forward_xpairs(mvae_ctx* ctx, const mvae_xpairs* xpairs, const float* eps, void* stream);
+int mvae_train_step_xpairs(mvae_ctx* ctx, const mvae_xpairs* xpairs, const float* areas, const float* eps,
+                           float* losses_out, float* dist_out, void* stream);
+int mvae_predict_xpairs(mvae_ctx* ctx, const mvae_xpairs* xpairs, const float* eps, float* dist_out,
+                        void* stream);
+int mvae_predict_encode_xpairs(mvae_ctx* ctx, const mvae_xpairs* xpairs, const float* eps, void* stream);
+int mvae_transform_xpairs(mvae_ctx* ctx, const mvae_xpairs* xpairs, float* zmean_out, void* stream);
+int mvae_reconstruct_xpairs(mvae_ctx* ctx, const mvae_xpairs* xpairs, const float* eps, float* y_out,
+                            void* stream);
+
 /* ---- retrieval: embed a gallery, score every lock against every key ------------------ */
 /* Any number of single images from one uint8 table, encoded to their latent mean (and log-sigma):
  * what a trained metric model is used for. The call runs ceil(count / 3B) encoder passes; image t
@@ -462,6 +496,12 @@ int mvae_debug_pairs_bits(const unsigned char* locks, const unsigned char* keys,
                           const float* coef, int B, int S, float divisor, int mode, int no_xbw, float* x,
                           unsigned* xbf, unsigned* xbw, unsigned char* xbits, int ldbits, int* dyn,
                           unsigned short* plane, int ldx, void* stream);
+/* mvae_debug_pairs_bits, modes 0 and 1 only, with the key of each row from key_idx (NULL: idx);
+ * keys may hold another number of images than locks. */
+int mvae_debug_xpairs_bits(const unsigned char* locks, const unsigned char* keys, const int* idx,
+                           const int* key_idx, const float* coef, int B, int S, float divisor, int mode,
+                           int no_xbw, float* x, unsigned* xbf, unsigned* xbw, unsigned char* xbits,
+                           int ldbits, int* dyn, unsigned short* plane, int ldx, void* stream);
 int mvae_debug_gemm(int M, int N, int K, const float* A, int lda, int at, const float* B, int ldb,
                     int bt, float* C, int ldc, int epi, int act, const float* aux, int ld_aux,
                     void* stream);

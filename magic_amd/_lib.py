@@ -52,6 +52,12 @@ class mvae_pairs(C.Structure):
                 ("idx", C.c_void_p), ("coef", C.c_void_p), ("divisor", C.c_float)]
 
 
+class mvae_xpairs(C.Structure):
+    """``mvae_pairs`` with a key index of its own (``include/mvae.h``): row b is lock ``p.idx[b]`` and
+    key ``key_idx[b]``."""
+    _fields_ = [("p", mvae_pairs), ("key_idx", C.c_void_p)]
+
+
 class mvae_images(C.Structure):
     """Single images of one uint8 table (``include/mvae.h``): device pointers and sizes."""
     _fields_ = [("table", C.c_void_p), ("height", C.c_int), ("width", C.c_int), ("idx", C.c_void_p),
@@ -111,6 +117,16 @@ _SIGS = {
     "mvae_transform_pairs": ([C.c_void_p, C.POINTER(mvae_pairs), C.c_void_p, C.c_void_p], C.c_int),
     "mvae_reconstruct_pairs": ([C.c_void_p, C.POINTER(mvae_pairs), C.c_void_p, C.c_void_p, C.c_void_p],
                                C.c_int),
+    "mvae_make_batch_x": ([C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                           C.c_float, C.c_void_p, C.c_void_p], C.c_int),
+    "mvae_forward_xpairs": ([C.c_void_p, C.POINTER(mvae_xpairs), C.c_void_p, C.c_void_p], C.c_int),
+    "mvae_train_step_xpairs": ([C.c_void_p, C.POINTER(mvae_xpairs), C.c_void_p, C.c_void_p, C.c_void_p,
+                                C.c_void_p, C.c_void_p], C.c_int),
+    "mvae_predict_xpairs": ([C.c_void_p, C.POINTER(mvae_xpairs), C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+    "mvae_predict_encode_xpairs": ([C.c_void_p, C.POINTER(mvae_xpairs), C.c_void_p, C.c_void_p], C.c_int),
+    "mvae_transform_xpairs": ([C.c_void_p, C.POINTER(mvae_xpairs), C.c_void_p, C.c_void_p], C.c_int),
+    "mvae_reconstruct_xpairs": ([C.c_void_p, C.POINTER(mvae_xpairs), C.c_void_p, C.c_void_p, C.c_void_p],
+                                C.c_int),
     "mvae_embed_images": ([C.c_void_p, C.POINTER(mvae_images), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
                           C.c_int),
     "mvae_match": ([C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p,
@@ -141,6 +157,9 @@ _SIGS = {
     "mvae_debug_pairs_bits": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float,
                                C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                C.c_void_p, C.c_void_p, C.c_int, C.c_void_p], C.c_int),
+    "mvae_debug_xpairs_bits": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p], C.c_int),
     "mvae_debug_gemm": ([C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                          C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                          C.c_int, C.c_void_p], C.c_int),

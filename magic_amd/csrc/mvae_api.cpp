@@ -1224,7 +1224,8 @@ enum { ENC_TRAIN = 0, ENC_EVAL = 1, ENC_MEAN = 2 };
 // The batch is x, or (x == NULL) the pairs descriptor. A pairs batch takes the direct kernel
 // (launch_pairs_bits: the BitMats straight from the tables) exactly where an x batch would take the
 // bits branch below and the launcher's shape / alignment conditions hold; in every other
-// configuration X is materialised into the context's scratch and the x code runs on it.
+// configuration X is materialised into the context's scratch and the x code runs on it. kidx (the
+// *_xpairs entry points): the key of each row, NULL for the own pair (pairs->idx).
 //
 // One pass of mvae_embed_images (x and pairs NULL): the 3B images [first, first + 3B) of the call,
 // image t of the pass being stacked row t; it takes its direct kernel (launch_images_bits) under
@@ -1236,7 +1237,7 @@ struct EmbedPass {
   int nvalid;      // min(3B, count - first)
 };
 static int encode(mvae_ctx* ctx, const float* x, const float* eps, hipStream_t st, int draw = ENC_TRAIN,
-                  const mvae_pairs* pairs = nullptr, const EmbedPass* ep = nullptr) {
+                  const mvae_pairs* pairs = nullptr, const EmbedPass* ep = nullptr, const int* kidx = nullptr) {
   auto c = ctx;
   const bool direct = c->bits_on && ((pairs && pairs_bits_fits(pairs->locks, pairs->keys, pairs->coef, c->B, c->D)) ||
                                      (ep && images_bits_fits(ep->table, c->B, c->D)));
@@ -1259,7 +1260,7 @@ static int encode(mvae_ctx* ctx, const float* x, const float* eps, hipStream_t s
     }
     if (pairs) {
       TIMED("pairs_make_batch");
-      MV_CHECK(launch_make_batch(pairs->locks, pairs->keys, pairs->height, pairs->width, pairs->idx, pairs->coef,
+      MV_CHECK(launch_make_batch(pairs->locks, pairs->keys, pairs->height, pairs->width, pairs->idx, kidx, pairs->coef,
                                  c->B, pairs->divisor, c->pairs_x, st));
     } else {
       TIMED("images_make_x");
@@ -1281,8 +1282,8 @@ static int encode(mvae_ctx* ctx, const float* x, const float* eps, hipStream_t s
                                     c->B, c->xbf, c->kts_f, c->xbw, c->kts_w, c->xbits, c->ldbits, cur, prev, c->xs,
                                     planes_of(c, c->xs), c->ldx, c->x32dyn, true, st));
       else if (direct)
-        MV_CHECK(launch_pairs_bits(pairs->locks, pairs->keys, pairs->height, pairs->width, pairs->idx, pairs->coef,
-                                   pairs->divisor, c->B, c->xbf, c->kts_f, c->xbw, c->kts_w, c->xbits, c->ldbits,
+        MV_CHECK(launch_pairs_bits(pairs->locks, pairs->keys, pairs->height, pairs->width, pairs->idx, kidx,
+                                   pairs->coef, pairs->divisor, c->B, c->xbf, c->kts_f, c->xbw, c->kts_w, c->xbits, c->ldbits,
                                    cur, prev, c->xs, planes_of(c, c->xs), c->ldx, c->x32dyn, split, st));
       else
         MV_CHECK(launch_deint_bits(x, c->B, c->D, c->xbf, c->kts_f, c->xbw, c->kts_w, c->xbits, c->ldbits, cur,
@@ -1388,9 +1389,10 @@ static int check_pairs(mvae_ctx* ctx, const mvae_pairs* p, const char* who) {
   return MVAE_OK;
 }
 
-static int forward_any(mvae_ctx* ctx, const float* x, const mvae_pairs* pairs, const float* eps, void* stream) {
+static int forward_any(mvae_ctx* ctx, const float* x, const mvae_pairs* pairs, const float* eps, void* stream,
+                       const int* kidx = nullptr) {
   hipStream_t st = (hipStream_t)stream;
-  int rc = encode(ctx, x, eps, st, ENC_TRAIN, pairs);
+  int rc = encode(ctx, x, eps, st, ENC_TRAIN, pairs, nullptr, kidx);
   if (rc) return rc;
   if ((rc = decode_hidden(ctx, st))) return rc;
   if (ctx->f_split && ctx->use_split) {
@@ -1412,6 +1414,17 @@ extern "C" int mvae_forward_pairs(mvae_ctx* ctx, const mvae_pairs* pairs, const 
   if (!ctx) return MVAE_EINVAL;
   if (int rc = check_pairs(ctx, pairs, "mvae_forward_pairs")) return rc;
   return forward_any(ctx, nullptr, pairs, eps, stream);
+}
+
+// the *_xpairs twins: the *_pairs code with the key of each row from key_idx
+static int check_xpairs(mvae_ctx* ctx, const mvae_xpairs* xp, const char* who) {
+  return check_pairs(ctx, xp ? &xp->p : nullptr, who);
+}
+
+extern "C" int mvae_forward_xpairs(mvae_ctx* ctx, const mvae_xpairs* xp, const float* eps, void* stream) {
+  if (!ctx) return MVAE_EINVAL;
+  if (int rc = check_xpairs(ctx, xp, "mvae_forward_xpairs")) return rc;
+  return forward_any(ctx, nullptr, &xp->p, eps, stream, xp->key_idx);
 }
 
 extern "C" int mvae_metric(mvae_ctx* ctx, const float* areas, void* stream) {
@@ -1738,9 +1751,10 @@ extern "C" int mvae_adam(mvae_ctx* ctx, void* stream) {
 }
 
 static int train_step_any(mvae_ctx* ctx, const float* x, const mvae_pairs* pairs, const float* areas,
-                          const float* eps, float* losses_out, float* dist_out, void* stream) {
+                          const float* eps, float* losses_out, float* dist_out, void* stream,
+                          const int* kidx = nullptr) {
   int rc;
-  if ((rc = forward_any(ctx, x, pairs, eps, stream))) return rc;
+  if ((rc = forward_any(ctx, x, pairs, eps, stream, kidx))) return rc;
   if ((rc = mvae_metric(ctx, areas, stream))) return rc;
   hipStream_t st = (hipStream_t)stream;
   if (losses_out) MV_CHECK(hipMemcpyAsync(losses_out, ctx->losses, 5 * sizeof(float), hipMemcpyDeviceToDevice, st));
@@ -1769,11 +1783,18 @@ extern "C" int mvae_train_step_pairs(mvae_ctx* ctx, const mvae_pairs* pairs, con
   return train_step_any(ctx, nullptr, pairs, areas, eps, losses_out, dist_out, stream);
 }
 
+extern "C" int mvae_train_step_xpairs(mvae_ctx* ctx, const mvae_xpairs* xp, const float* areas, const float* eps,
+                                      float* losses_out, float* dist_out, void* stream) {
+  if (!ctx || !areas) return MVAE_EINVAL;
+  if (int rc = check_xpairs(ctx, xp, "mvae_train_step_xpairs")) return rc;
+  return train_step_any(ctx, nullptr, &xp->p, areas, eps, losses_out, dist_out, stream, xp->key_idx);
+}
+
 // get_predictions in two phases (a data-parallel host all-reduces MVAE_BUF_COLSQ between them:
 // the cosine distance normalises over the GLOBAL batch, 8c/vae.py:449-450)
 static int predict_encode_any(mvae_ctx* ctx, const float* x, const mvae_pairs* pairs, const float* eps,
-                              void* stream) {
-  int rc = encode(ctx, x, eps, (hipStream_t)stream, ENC_EVAL, pairs);
+                              void* stream, const int* kidx = nullptr) {
+  int rc = encode(ctx, x, eps, (hipStream_t)stream, ENC_EVAL, pairs, nullptr, kidx);
   if (rc) return rc;
   ctx->phase = 6;
   return MVAE_OK;
@@ -1788,6 +1809,12 @@ extern "C" int mvae_predict_encode_pairs(mvae_ctx* ctx, const mvae_pairs* pairs,
   if (!ctx) return MVAE_EINVAL;
   if (int rc = check_pairs(ctx, pairs, "mvae_predict_encode_pairs")) return rc;
   return predict_encode_any(ctx, nullptr, pairs, eps, stream);
+}
+
+extern "C" int mvae_predict_encode_xpairs(mvae_ctx* ctx, const mvae_xpairs* xp, const float* eps, void* stream) {
+  if (!ctx) return MVAE_EINVAL;
+  if (int rc = check_xpairs(ctx, xp, "mvae_predict_encode_xpairs")) return rc;
+  return predict_encode_any(ctx, nullptr, &xp->p, eps, stream, xp->key_idx);
 }
 
 extern "C" int mvae_predict_finish(mvae_ctx* ctx, float* dist_out, void* stream) {
@@ -1815,9 +1842,18 @@ extern "C" int mvae_predict_pairs(mvae_ctx* ctx, const mvae_pairs* pairs, const 
   return rc ? rc : mvae_predict_finish(ctx, dist_out, stream);
 }
 
-static int transform_any(mvae_ctx* ctx, const float* x, const mvae_pairs* pairs, float* zmean_out, void* stream) {
+extern "C" int mvae_predict_xpairs(mvae_ctx* ctx, const mvae_xpairs* xp, const float* eps, float* dist_out,
+                                   void* stream) {
+  if (!ctx || !dist_out) return MVAE_EINVAL;
+  if (int rc = check_xpairs(ctx, xp, "mvae_predict_xpairs")) return rc;
+  int rc = predict_encode_any(ctx, nullptr, &xp->p, eps, stream, xp->key_idx);
+  return rc ? rc : mvae_predict_finish(ctx, dist_out, stream);
+}
+
+static int transform_any(mvae_ctx* ctx, const float* x, const mvae_pairs* pairs, float* zmean_out, void* stream,
+                         const int* kidx = nullptr) {
   hipStream_t st = (hipStream_t)stream;
-  int rc = encode(ctx, x, nullptr, st, ENC_MEAN, pairs);
+  int rc = encode(ctx, x, nullptr, st, ENC_MEAN, pairs, nullptr, kidx);
   if (rc) return rc;
   MV_CHECK(launch_copy2d(ctx->ms + (size_t)ctx->B * 2 * ctx->L, 2 * ctx->L, zmean_out, ctx->L,
                          ctx->B, ctx->L, st));
@@ -1834,6 +1870,12 @@ extern "C" int mvae_transform_pairs(mvae_ctx* ctx, const mvae_pairs* pairs, floa
   if (!ctx || !zmean_out) return MVAE_EINVAL;
   if (int rc = check_pairs(ctx, pairs, "mvae_transform_pairs")) return rc;
   return transform_any(ctx, nullptr, pairs, zmean_out, stream);
+}
+
+extern "C" int mvae_transform_xpairs(mvae_ctx* ctx, const mvae_xpairs* xp, float* zmean_out, void* stream) {
+  if (!ctx || !zmean_out) return MVAE_EINVAL;
+  if (int rc = check_xpairs(ctx, xp, "mvae_transform_xpairs")) return rc;
+  return transform_any(ctx, nullptr, &xp->p, zmean_out, stream, xp->key_idx);
 }
 
 // ceil(count / 3B) encoder passes, every stacked row a wanted image; the means (and log-sigmas) of
@@ -2053,9 +2095,9 @@ extern "C" int mvae_match_merge(mvae_ctx* ctx, const float* vals, const int* idx
 }
 
 static int reconstruct_any(mvae_ctx* ctx, const float* x, const mvae_pairs* pairs, const float* eps, float* y_out,
-                           void* stream) {
+                           void* stream, const int* kidx = nullptr) {
   hipStream_t st = (hipStream_t)stream;
-  int rc = encode(ctx, x, eps, st, ENC_EVAL, pairs);
+  int rc = encode(ctx, x, eps, st, ENC_EVAL, pairs, nullptr, kidx);
   if (rc) return rc;
   if ((rc = decode_hidden(ctx, st))) return rc;
   GemmDesc d = ctx->f_out;
@@ -2076,6 +2118,13 @@ extern "C" int mvae_reconstruct_pairs(mvae_ctx* ctx, const mvae_pairs* pairs, co
   if (!ctx || !y_out) return MVAE_EINVAL;
   if (int rc = check_pairs(ctx, pairs, "mvae_reconstruct_pairs")) return rc;
   return reconstruct_any(ctx, nullptr, pairs, eps, y_out, stream);
+}
+
+extern "C" int mvae_reconstruct_xpairs(mvae_ctx* ctx, const mvae_xpairs* xp, const float* eps, float* y_out,
+                                       void* stream) {
+  if (!ctx || !y_out) return MVAE_EINVAL;
+  if (int rc = check_xpairs(ctx, xp, "mvae_reconstruct_xpairs")) return rc;
+  return reconstruct_any(ctx, nullptr, &xp->p, eps, y_out, stream, xp->key_idx);
 }
 
 extern "C" int mvae_generate(mvae_ctx* ctx, const float* zin, int n, float* y_out, void* stream) {
@@ -2564,7 +2613,23 @@ extern "C" int mvae_make_batch(const unsigned char* locks, const unsigned char* 
     return fail(nullptr, MVAE_EINVAL, "mvae_make_batch: bad argument");
   if ((reinterpret_cast<uintptr_t>(coef) & 15) != 0)
     return fail(nullptr, MVAE_EINVAL, "mvae_make_batch: coef must be 16-byte aligned");
-  hipError_t e = launch_make_batch(locks, keys, height, width, idx, coef, batch, divisor, x_out,
+  hipError_t e = launch_make_batch(locks, keys, height, width, idx, nullptr, coef, batch, divisor, x_out,
+                                   (hipStream_t)stream);
+  if (e != hipSuccess) { g_create_err = hipGetErrorString(e); return (int)e; }
+  return MVAE_OK;
+}
+
+extern "C" int mvae_make_batch_x(const unsigned char* locks, const unsigned char* keys, int height, int width,
+                                 const int* lock_idx, const int* key_idx, const float* coef, int batch,
+                                 float divisor, float* x_out, void* stream) {
+  if (!locks || !keys || !lock_idx || !coef || !x_out)
+    return fail(nullptr, MVAE_EINVAL, "mvae_make_batch_x: null locks, keys, lock_idx, coef or x_out");
+  if (height <= 0 || width <= 0 || batch <= 0)
+    return fail(nullptr, MVAE_EINVAL, "mvae_make_batch_x: height, width and batch must be positive");
+  if (!(divisor > 0.f)) return fail(nullptr, MVAE_EINVAL, "mvae_make_batch_x: divisor must be positive");
+  if ((reinterpret_cast<uintptr_t>(coef) & 15) != 0)
+    return fail(nullptr, MVAE_EINVAL, "mvae_make_batch_x: coef must be 16-byte aligned");
+  hipError_t e = launch_make_batch(locks, keys, height, width, lock_idx, key_idx, coef, batch, divisor, x_out,
                                    (hipStream_t)stream);
   if (e != hipSuccess) { g_create_err = hipGetErrorString(e); return (int)e; }
   return MVAE_OK;
@@ -2671,26 +2736,27 @@ extern "C" int mvae_debug_conv2(int S1, int B, int mode, int mfma, const float* 
 // xbf bitmat_words(3B, D + 1) words, xbw bitmat_words(D + 1, 3B) words, xbits [B][ldbits] bytes,
 // dyn 4 ints, plane [3B][ldx] bf16 (plane 0, written when the not-binary word rises), x [B][3D]
 // floats (mode 0 only).
-extern "C" int mvae_debug_pairs_bits(const unsigned char* locks, const unsigned char* keys, const int* idx,
-                                     const float* coef, int B, int S, float divisor, int mode, int no_xbw,
-                                     float* x, unsigned* xbf, unsigned* xbw, unsigned char* xbits, int ldbits,
-                                     int* dyn, unsigned short* plane, int ldx, void* stream) {
+static int debug_bits(const char* who, const unsigned char* locks, const unsigned char* keys, const int* idx,
+                      const int* kidx, const float* coef, int B, int S, float divisor, int mode, int no_xbw,
+                      float* x, unsigned* xbf, unsigned* xbw, unsigned char* xbits, int ldbits, int* dyn,
+                      unsigned short* plane, int ldx, void* stream) {
+  const std::string w(who);
   const bool pairs_mode = mode == 0 || mode == 1;
   if ((mode != 3 && (!locks || !idx)) || (pairs_mode && (!keys || !coef)) || B <= 0 || S <= 0 || S > 4096 ||
       !(divisor > 0.f) || mode < 0 || mode > 3 || ((mode == 0 || mode == 3) && !x) || !xbf || !xbw || !xbits || !dyn || !plane || ldx < S * S || ldbits < (S * S + 7) / 8)
-    return fail(nullptr, MVAE_EINVAL, "mvae_debug_pairs_bits: bad argument");
+    return fail(nullptr, MVAE_EINVAL, w + ": bad argument");
   hipStream_t st = (hipStream_t)stream;
   const int D = S * S;
   const Planes pl{plane, (long long)3 * B * ldx, 1};
   const int kts_f = bitmat_kts(D + 1), kts_w = bitmat_kts(3 * B);
   hipError_t e;
   if (mode == 0) {
-    e = launch_make_batch(locks, keys, S, S, idx, coef, B, divisor, x, st);
+    e = launch_make_batch(locks, keys, S, S, idx, kidx, coef, B, divisor, x, st);
     if (e == hipSuccess)
       e = launch_deint_bits(x, B, D, xbf, kts_f, xbw, kts_w, xbits, ldbits, dyn, dyn + 1, nullptr, pl, ldx, 0,
                             no_xbw != 0, st);
   } else if (mode == 1) {
-    e = launch_pairs_bits(locks, keys, S, S, idx, coef, divisor, B, xbf, kts_f, xbw, kts_w, xbits, ldbits, dyn,
+    e = launch_pairs_bits(locks, keys, S, S, idx, kidx, coef, divisor, B, xbf, kts_f, xbw, kts_w, xbits, ldbits, dyn,
                           dyn + 1, nullptr, pl, ldx, 0, no_xbw != 0, st);
   } else if (mode == 2) {
     e = launch_images_bits(locks, S, S, idx, 3 * B, divisor, B, xbf, kts_f, xbw, kts_w, xbits, ldbits, dyn, dyn + 1,
@@ -2701,10 +2767,28 @@ extern "C" int mvae_debug_pairs_bits(const unsigned char* locks, const unsigned 
                                                              nullptr, pl, ldx, 0, no_xbw != 0, st);
   }
   if (e == hipErrorInvalidValue)
-    return fail(nullptr, MVAE_EINVAL, "mvae_debug_pairs_bits: shape or alignment the kernels do not serve");
+    return fail(nullptr, MVAE_EINVAL, w + ": shape or alignment the kernels do not serve");
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   if (e != hipSuccess) { g_create_err = hipGetErrorString(e); return (int)e; }
   return MVAE_OK;
+}
+
+extern "C" int mvae_debug_pairs_bits(const unsigned char* locks, const unsigned char* keys, const int* idx,
+                                     const float* coef, int B, int S, float divisor, int mode, int no_xbw,
+                                     float* x, unsigned* xbf, unsigned* xbw, unsigned char* xbits, int ldbits,
+                                     int* dyn, unsigned short* plane, int ldx, void* stream) {
+  return debug_bits("mvae_debug_pairs_bits", locks, keys, idx, nullptr, coef, B, S, divisor, mode, no_xbw, x, xbf,
+                    xbw, xbits, ldbits, dyn, plane, ldx, stream);
+}
+
+// modes 0 and 1 with the key of each row from key_idx (NULL: idx)
+extern "C" int mvae_debug_xpairs_bits(const unsigned char* locks, const unsigned char* keys, const int* idx,
+                                      const int* key_idx, const float* coef, int B, int S, float divisor, int mode,
+                                      int no_xbw, float* x, unsigned* xbf, unsigned* xbw, unsigned char* xbits,
+                                      int ldbits, int* dyn, unsigned short* plane, int ldx, void* stream) {
+  if (mode != 0 && mode != 1) return fail(nullptr, MVAE_EINVAL, "mvae_debug_xpairs_bits: mode must be 0 or 1");
+  return debug_bits("mvae_debug_xpairs_bits", locks, keys, idx, key_idx, coef, B, S, divisor, mode, no_xbw, x, xbf,
+                    xbw, xbits, ldbits, dyn, plane, ldx, stream);
 }
 
 // The fused hidden-layer chain on caller buffers (tests only; synchronous; allocates nothing): fills a

@@ -243,19 +243,20 @@ hipError_t launch_split_planes(const float* src, size_t n, const Planes& dst, hi
 // x[i] = x[i] > 0 ? 1 : 0 (diagnostics: binary BCE targets for the GEMM harness)
 hipError_t launch_binarize(float* x, size_t n, hipStream_t st);
 hipError_t launch_make_batch(const unsigned char* locks, const unsigned char* keys, int H, int W,
-                             const int* idx, const float* coef, int B, float div, float* x,
-                             hipStream_t st);
+                             const int* idx, const int* kidx, const float* coef, int B, float div, float* x,
+                             hipStream_t st);  // kidx: the key of each row; NULL: idx
 // ---- a batch's bit operands straight from the uint8 tables (pairs_bits.hip) ----
 // What launch_make_batch followed by launch_deint_bits writes (the same bits: BitMats, target
 // bits, flag slots, and for a batch with a pixel other than 0 / 1 the planes, fp32 rows and inexact
 // flag of the grey pass), without X. no_xbw: the forward words only (as launch_deint_bits').
 // Serves D = H W % 8 == 0, B % 64 == 0, 8-byte aligned tables and a 16-byte aligned coef
-// (pairs_bits_fits); hipErrorInvalidValue otherwise, before anything is launched.
+// (pairs_bits_fits); hipErrorInvalidValue otherwise, before anything is launched. kidx: the key of
+// each row, an index into `keys` (NULL: idx, the own pair).
 bool pairs_bits_fits(const unsigned char* locks, const unsigned char* keys, const float* coef, int B, int D);
 hipError_t launch_pairs_bits(const unsigned char* locks, const unsigned char* keys, int H, int W, const int* idx,
-                             const float* coef, float div, int B, unsigned* xbf, int kts_f, unsigned* xbw,
-                             int kts_w, unsigned char* xbits, int ldbits, int* dyn, int* dyn_next, float* xs,
-                             const Planes& xp, int ldx, int f32dyn_mask, bool no_xbw, hipStream_t st);
+                             const int* kidx, const float* coef, float div, int B, unsigned* xbf, int kts_f,
+                             unsigned* xbw, int kts_w, unsigned char* xbits, int ldbits, int* dyn, int* dyn_next,
+                             float* xs, const Planes& xp, int ldx, int f32dyn_mask, bool no_xbw, hipStream_t st);
 // ---- an embedding pass's operand from one uint8 image table (images_bits.hip) ----
 // 3B independent images, image t of the pass = row t of the stacked operand (block t / B, batch row
 // t % B): table image idx[t] (t when idx is null) for t < nvalid, an all-zero image past that (idx

@@ -730,17 +730,22 @@ __global__ void copy2d_kernel(const float* __restrict__ s, int lds, float* __res
 // gather indices match the host restatement bit for bit (hipcc contracts even the *_rn
 // intrinsics into FMAs unless contraction is off: a few pixels per batch then sampled a
 // neighbour; caught by tests/test_input_pipeline.py's grey-value tables).
+// Row b is lock idx[b], its rotation, and key kidx[b] (the own pair passes idx for both).
 __global__ void make_batch_kernel(const unsigned char* __restrict__ locks,
                                   const unsigned char* __restrict__ keys, int H, int W,
-                                  const int* __restrict__ idx, const float4* __restrict__ coef,
-                                  float div, float* __restrict__ x) {
+                                  const int* __restrict__ idx, const int* __restrict__ kidx,
+                                  const float4* __restrict__ coef, float div, float* __restrict__ x) {
 #pragma clang fp contract(off)  // (the *_rn intrinsics do not prevent it: their bodies are outside)
   const int b = blockIdx.y;
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
   const int HW = H * W;
   if (p >= HW) return;
-  const int id = idx[b];
+  const int id = idx[b], kid = kidx[b];
   const float4 cf = coef[b];
+  // (the row's three scalar loads in flight together and waited for once: left to itself the
+  // scheduler issues the key's index or the coefficients only after waiting for the lock's index, a
+  // second round trip at the head of a short workgroup)
+  asm volatile("" ::"s"(id), "s"(kid), "s"(cf.x), "s"(cf.y), "s"(cf.z), "s"(cf.w));
   const int yy = p / W, xx = p - yy * W;
   const float fx = (float)xx, fy = (float)yy;
   const float xin = (cf.x * fx - cf.y * fy) + cf.z;  // unfused: fp contract(off) above
@@ -753,7 +758,7 @@ __global__ void make_batch_kernel(const unsigned char* __restrict__ locks,
   float* o = x + (size_t)b * 3 * HW + 3 * (size_t)p;
   o[0] = (float)L[p] / div;
   o[1] = rot / div;
-  o[2] = (float)keys[(size_t)id * HW + p] / div;
+  o[2] = (float)keys[(size_t)kid * HW + p] / div;
 }
 
 // The same batch (bit for bit) at 4 pixels per thread for H*W % 4 == 0 and a 16-B aligned x:
@@ -765,6 +770,7 @@ constexpr int MB_PIX = 4 * 256;  // pixels per workgroup
 __global__ __launch_bounds__(256) void make_batch4_kernel(const unsigned char* __restrict__ locks,
                                                           const unsigned char* __restrict__ keys, int H,
                                                           int W, const int* __restrict__ idx,
+                                                          const int* __restrict__ kidx,
                                                           const float4* __restrict__ coef, float div,
                                                           float* __restrict__ x) {
 #pragma clang fp contract(off)  // as make_batch_kernel: the coordinates are unfused mul / add / sub
@@ -774,12 +780,16 @@ __global__ __launch_bounds__(256) void make_batch4_kernel(const unsigned char* _
   const int HW = H * W;
   const int s0 = blockIdx.x * MB_PIX;  // first pixel of the segment
   const int p0 = s0 + 4 * tid;
-  const int id = idx[b];
+  const int id = idx[b], kid = kidx[b];
   const float4 cf = coef[b];
+  // (the row's three scalar loads in flight together and waited for once: left to itself the
+  // scheduler issues the key's index or the coefficients only after waiting for the lock's index, a
+  // second round trip at the head of a short workgroup)
+  asm volatile("" ::"s"(id), "s"(kid), "s"(cf.x), "s"(cf.y), "s"(cf.z), "s"(cf.w));
   const unsigned char* L = locks + (size_t)id * HW;
   if (p0 < HW) {
     const uchar4 lv = *reinterpret_cast<const uchar4*>(L + p0);
-    const uchar4 kv = *reinterpret_cast<const uchar4*>(keys + (size_t)id * HW + p0);
+    const uchar4 kv = *reinterpret_cast<const uchar4*>(keys + (size_t)kid * HW + p0);
     const unsigned char l[4] = {lv.x, lv.y, lv.z, lv.w}, k[4] = {kv.x, kv.y, kv.z, kv.w};
     float v[12];
 #pragma unroll
@@ -1075,17 +1085,18 @@ hipError_t launch_binarize(float* x, size_t n, hipStream_t st) {
 }
 
 hipError_t launch_make_batch(const unsigned char* locks, const unsigned char* keys, int H, int W,
-                             const int* idx, const float* coef, int B, float div, float* x,
+                             const int* idx, const int* kidx, const float* coef, int B, float div, float* x,
                              hipStream_t st) {
+  if (!kidx) kidx = idx;  // the own pair
   const size_t hw = (size_t)H * W;
   if (hw % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0) {
     dim3 g(nblocks(hw, MB_PIX), B);
-    hipLaunchKernelGGL(make_batch4_kernel, g, dim3(256), 0, st, locks, keys, H, W, idx,
+    hipLaunchKernelGGL(make_batch4_kernel, g, dim3(256), 0, st, locks, keys, H, W, idx, kidx,
                        reinterpret_cast<const float4*>(coef), div, x);
     return hipGetLastError();
   }
   dim3 g(nblocks(hw, 256), B);
-  hipLaunchKernelGGL(make_batch_kernel, g, dim3(256), 0, st, locks, keys, H, W, idx,
+  hipLaunchKernelGGL(make_batch_kernel, g, dim3(256), 0, st, locks, keys, H, W, idx, kidx,
                      reinterpret_cast<const float4*>(coef), div, x);
   return hipGetLastError();
 }

@@ -1,10 +1,11 @@
 // The layer-0 bit operands of a 0/1 batch straight from the uint8 lock / key tables (gfx950): the
 // batch producer (make_batch_kernel, mvae_kernels.hip) and the de-interleave to bits
 // (deint_bits_kernel) in one pass, without the fp32 X [B, 3 D] between them. A batch is described
-// by (tables, idx, rotation coefficients): row b is example idx[b], its rotated lock gathered by
-// make_batch_kernel's arithmetic. Per pixel triple the pass reads 2 table bytes (plus the gathers,
-// which stay in cache: the rotated image is the lock image just read) and writes the ~1.1 bits of
-// the BitMats and target bits, where the two kernels write and read back 12 bytes of X.
+// by (tables, idx, kidx, rotation coefficients): row b is lock idx[b] and key kidx[b] (the own pair
+// passes idx for both), its rotated lock gathered by make_batch_kernel's arithmetic. Per pixel
+// triple the pass reads 2 table bytes (plus the gathers, which stay in cache: the rotated image is
+// the lock image just read) and writes the ~1.1 bits of the BitMats and target bits, where the two
+// kernels write and read back 12 bytes of X.
 //
 // The 24 values of an octet are formed as the producer forms them, (float)byte / div, and the bit
 // and the not-binary test derived from that float by deint_octet: the not-binary word rises for
@@ -28,11 +29,11 @@ struct PairRow {
 };
 __device__ __forceinline__ PairRow pair_row(const unsigned char* __restrict__ locks,
                                             const unsigned char* __restrict__ keys, int HW,
-                                            const int* __restrict__ idx, const float4* __restrict__ coef, int b) {
-  const int id = idx[b];
+                                            const int* __restrict__ idx, const int* __restrict__ kidx,
+                                            const float4* __restrict__ coef, int b) {
   PairRow r;
-  r.L = locks + (size_t)id * HW;
-  r.K = keys + (size_t)id * HW;
+  r.L = locks + (size_t)idx[b] * HW;
+  r.K = keys + (size_t)kidx[b] * HW;
   r.cf = coef[b];
   return r;
 }
@@ -77,6 +78,7 @@ template <bool NOW>
 __global__ __launch_bounds__(256) void pairs_bits_kernel(const unsigned char* __restrict__ locks,
                                                          const unsigned char* __restrict__ keys, int H, int W,
                                                          const int* __restrict__ idx,
+                                                         const int* __restrict__ kidx,
                                                          const float4* __restrict__ coef, float div, int B, int D,
                                                          int kts_f, int kts_w, unsigned* __restrict__ xbf,
                                                          unsigned* __restrict__ xbw,
@@ -94,7 +96,8 @@ __global__ __launch_bounds__(256) void pairs_bits_kernel(const unsigned char* __
   if (in) {  // every row's loads before the first use
     PairRow row[S::NR];
 #pragma unroll
-    for (int i = 0; i < S::NR; ++i) row[i] = pair_row(locks, keys, D, idx, coef, b0 + tid / S::NO + S::RPP * i);
+    for (int i = 0; i < S::NR; ++i)
+      row[i] = pair_row(locks, keys, D, idx, kidx, coef, b0 + tid / S::NO + S::RPP * i);
 #pragma unroll
     for (int i = 0; i < S::NR; ++i) pb[i] = pair_load(row[i], H, W, pix);
   }
@@ -114,9 +117,10 @@ __global__ __launch_bounds__(256) void pairs_bits_kernel(const unsigned char* __
 // deint_grey_kernel's pass (only after pairs_bits_kernel raised the not-binary word; else every
 // workgroup returns at once) with each octet's 24 values rebuilt from the tables
 __global__ void pairs_grey_kernel(const unsigned char* __restrict__ locks, const unsigned char* __restrict__ keys,
-                                  int H, int W, const int* __restrict__ idx, const float4* __restrict__ coef,
-                                  float div, float* __restrict__ xs, unsigned short* __restrict__ xp, long long ps,
-                                  int np, int f32mask, int* __restrict__ dyn, int B, int D, int ldx) {
+                                  int H, int W, const int* __restrict__ idx, const int* __restrict__ kidx,
+                                  const float4* __restrict__ coef, float div, float* __restrict__ xs,
+                                  unsigned short* __restrict__ xp, long long ps, int np, int f32mask,
+                                  int* __restrict__ dyn, int B, int D, int ldx) {
   if (dyn[2] == 0) return;
   const int nq = D / 8;
   const size_t n = (size_t)B * nq;
@@ -124,7 +128,7 @@ __global__ void pairs_grey_kernel(const unsigned char* __restrict__ locks, const
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
     const int b = (int)(i / nq), q = (int)(i % nq);
     float e[24];
-    pair_values(pair_load(pair_row(locks, keys, D, idx, coef, b), H, W, 8 * q), div, e);
+    pair_values(pair_load(pair_row(locks, keys, D, idx, kidx, coef, b), H, W, 8 * q), div, e);
     const float4 v[6] = {make_float4(e[0], e[1], e[2], e[3]),     make_float4(e[4], e[5], e[6], e[7]),
                          make_float4(e[8], e[9], e[10], e[11]),   make_float4(e[12], e[13], e[14], e[15]),
                          make_float4(e[16], e[17], e[18], e[19]), make_float4(e[20], e[21], e[22], e[23])};
@@ -141,9 +145,9 @@ bool pairs_bits_fits(const unsigned char* locks, const unsigned char* keys, cons
 }
 
 hipError_t launch_pairs_bits(const unsigned char* locks, const unsigned char* keys, int H, int W, const int* idx,
-                             const float* coef, float div, int B, unsigned* xbf, int kts_f, unsigned* xbw,
-                             int kts_w, unsigned char* xbits, int ldbits, int* dyn, int* dyn_next, float* xs,
-                             const Planes& xp, int ldx, int f32dyn_mask, bool no_xbw, hipStream_t st) {
+                             const int* kidx, const float* coef, float div, int B, unsigned* xbf, int kts_f,
+                             unsigned* xbw, int kts_w, unsigned char* xbits, int ldbits, int* dyn, int* dyn_next,
+                             float* xs, const Planes& xp, int ldx, int f32dyn_mask, bool no_xbw, hipStream_t st) {
   const long long HW = (long long)H * W;
   if (H <= 0 || W <= 0 || HW > (1 << 30) || B <= 0) return hipErrorInvalidValue;
   const int D = (int)HW;
@@ -151,17 +155,18 @@ hipError_t launch_pairs_bits(const unsigned char* locks, const unsigned char* ke
       !xbf || !xbits || (!no_xbw && !xbw) || kts_f != bitmat_kts(D + 1) || kts_w != bitmat_kts(3 * B) ||
       ldbits < D / 8)
     return hipErrorInvalidValue;
+  if (!kidx) kidx = idx;  // the own pair
   const float4* c4 = reinterpret_cast<const float4*>(coef);
   const dim3 g((kts_f + 1) / 2, B / 64);
   if (no_xbw)
-    hipLaunchKernelGGL(pairs_bits_kernel<true>, g, dim3(256), 0, st, locks, keys, H, W, idx, c4, div, B, D, kts_f,
-                       kts_w, xbf, xbw, xbits, ldbits, dyn, dyn_next);
+    hipLaunchKernelGGL(pairs_bits_kernel<true>, g, dim3(256), 0, st, locks, keys, H, W, idx, kidx, c4, div, B, D,
+                       kts_f, kts_w, xbf, xbw, xbits, ldbits, dyn, dyn_next);
   else
-    hipLaunchKernelGGL(pairs_bits_kernel<false>, g, dim3(256), 0, st, locks, keys, H, W, idx, c4, div, B, D, kts_f,
-                       kts_w, xbf, xbw, xbits, ldbits, dyn, dyn_next);
+    hipLaunchKernelGGL(pairs_bits_kernel<false>, g, dim3(256), 0, st, locks, keys, H, W, idx, kidx, c4, div, B, D,
+                       kts_f, kts_w, xbf, xbw, xbits, ldbits, dyn, dyn_next);
   // (256 workgroups striding, as launch_deint_grey: for a 0/1 batch every one returns at once)
-  hipLaunchKernelGGL(pairs_grey_kernel, dim3(256), dim3(256), 0, st, locks, keys, H, W, idx, c4, div, xs, xp.p,
-                     xp.stride, xp.n, f32dyn_mask, dyn, B, D, ldx);
+  hipLaunchKernelGGL(pairs_grey_kernel, dim3(256), dim3(256), 0, st, locks, keys, H, W, idx, kidx, c4, div, xs,
+                     xp.p, xp.stride, xp.n, f32dyn_mask, dyn, B, D, ldx);
   return hipGetLastError();
 }
 

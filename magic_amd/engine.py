@@ -193,24 +193,38 @@ class Engine:
 
     def _pairs(self, pb: PairBatch):
         """The ``mvae_pairs`` descriptor of a ``PairBatch`` (tensors re-checked: they are mutable
-        attributes). Square tables only, as ``cfg.image_size``."""
+        attributes), or ``mvae_xpairs`` when it carries a ``key_idx``: the key table then only has to
+        share H and W with the lock table. Square tables only, as ``cfg.image_size``."""
+        kidx = getattr(pb, "key_idx", None)
         for t, dt in ((pb.locks, torch.uint8), (pb.keys, torch.uint8), (pb.idx, torch.int32),
                       (pb.coef, torch.float32)):
             if not t.is_cuda or t.dtype != dt or not t.is_contiguous():
                 raise ValueError("PairBatch: contiguous device tensors (uint8 tables, int32 idx, float32 coef) "
                                  "expected")
-        if pb.keys.shape != pb.locks.shape or tuple(pb.coef.shape) != (self.cfg.batch, 4):
-            raise ValueError("PairBatch: lock / key tables of one shape and coef [B, 4] expected")
-        p = _lib.mvae_pairs()
+        same = pb.keys.shape == pb.locks.shape if kidx is None else \
+            (pb.locks.dim() == 3 and pb.keys.dim() == 3 and pb.keys.shape[1:] == pb.locks.shape[1:])
+        if not same or tuple(pb.coef.shape) != (self.cfg.batch, 4):
+            raise ValueError("PairBatch: lock / key tables of one shape (with key_idx: of one H, W) and "
+                             "coef [B, 4] expected")
+        xp = None
+        if kidx is not None:
+            if tuple(kidx.shape) != tuple(pb.idx.shape):
+                raise ValueError("PairBatch: key_idx must have idx's shape")
+            xp = _lib.mvae_xpairs()
+            xp.key_idx = _iptr(kidx)
+        p = xp.p if xp is not None else _lib.mvae_pairs()
         p.locks, p.keys = pb.locks.data_ptr(), pb.keys.data_ptr()
         p.height, p.width = int(pb.locks.shape[1]), int(pb.locks.shape[2])
         p.idx, p.coef = pb.idx.data_ptr(), pb.coef.data_ptr()
         p.divisor = 255.0 if pb.normalize else 1.0
-        return p
+        return xp if xp is not None else p
 
     def _call(self, name: str, x, *args):
-        """``mvae_<name>`` on an X tensor, ``mvae_<name>_pairs`` on a ``PairBatch``."""
+        """``mvae_<name>`` on an X tensor, ``mvae_<name>_pairs`` on a ``PairBatch``,
+        ``mvae_<name>_xpairs`` on one with a ``key_idx``."""
         xin = self._xin(x)
+        if isinstance(xin, _lib.mvae_xpairs):
+            return self._check(getattr(self.lib, f"mvae_{name}_xpairs")(self.ctx, C.byref(xin), *args))
         if isinstance(xin, _lib.mvae_pairs):
             return self._check(getattr(self.lib, f"mvae_{name}_pairs")(self.ctx, C.byref(xin), *args))
         return self._check(getattr(self.lib, f"mvae_{name}")(self.ctx, xin, *args))

@@ -48,14 +48,15 @@ def _host(a):
 
 
 def train(vae, batches, n_samples: int, training_epochs: int = 60, driver: str = "11a",
-          invert=None, paired_eval=None, eval_at=None, display_step: int = 5, log=print):
+          invert=None, paired_eval=None, eval_at=None, display_step: int = 5, log=print, on_epoch=None):
     """Run the reference training loop. ``batches`` yields (images, labels) like the
     reference's ``sess.run([images_batch, labels_batch])``.
 
     invert: ``1/pred`` before the MSE; default: the driver's choice for a reciprocal model
     (11a inverts because its distance is the reciprocal, ``11a/vae.py:307,309``; a model
     without the reciprocal is never inverted). Returns (vae, history): history holds
-    ("mse", epoch, i, mse) and ("epoch", epoch, avg_cost, avg_loss) records."""
+    ("mse", epoch, i, mse) and ("epoch", epoch, avg_cost, avg_loss) records. ``on_epoch(epoch)``
+    is called before each epoch's first batch (``--pairs mined`` refreshes its candidates there)."""
     d = DRIVERS[driver]
     eval_at = eval_at or d["eval_at"]
     paired = d["paired"] if paired_eval is None else paired_eval
@@ -65,6 +66,8 @@ def train(vae, batches, n_samples: int, training_epochs: int = 60, driver: str =
     history = []
     try:
         for epoch in range(training_epochs):
+            if on_epoch is not None:
+                on_epoch(epoch)
             avg_cost = 0.0
             avg_loss = 0.0
             total_batch = int(n_samples / batch_size)
@@ -136,16 +139,38 @@ def main(argv=None):
                          "lock / key pair of the pool, computed on the GPU before training")
     ap.add_argument("--label-angles", type=int, default=360, metavar="R",
                     help="with --labels computed: the key is tried at R equally spaced rotations")
+    ap.add_argument("--pairs", choices=("own", "cross", "mined"), default="own",
+                    help="own: row b is pair i of the pool; cross: any lock with any key, the key drawn "
+                         "uniformly; mined: the key drawn from the K keys the model ranks first for the lock. "
+                         "cross and mined need --labels computed (the label is the pair's maximum overlap, "
+                         "computed when a pair is first drawn); the evaluation batches are drawn the same way")
+    ap.add_argument("--cross", type=float, default=1.0, metavar="P",
+                    help="with --pairs cross / mined: the share of rows that take a drawn key (the rest keep "
+                         "their own): the knob while the label cache fills")
+    ap.add_argument("--mine-k", type=int, default=16, metavar="K",
+                    help="with --pairs mined: candidates per lock (K <= 64)")
+    ap.add_argument("--mine-every", type=int, default=1, metavar="E",
+                    help="with --pairs mined: refresh the candidates every E epochs")
     args = ap.parse_args(argv)
+    if args.pairs != "own" and args.labels != "computed":
+        ap.error(f"--pairs {args.pairs} needs --labels computed")
+    if not 0.0 <= args.cross <= 1.0 or args.mine_k < 1 or args.mine_every < 1:
+        ap.error("--cross must be in [0, 1], --mine-k and --mine-every at least 1")
     cfg = preset(args.preset, image_size=args.image_size, batch=args.batch or None)
     eight_c = args.preset in ("8c", "8d", "8e", "8f")
     driver = args.driver or ("8c" if eight_c else "11a")
     vae = TangoEncoder(None, config=cfg, compat="8c" if eight_c else "11a")
     batches = overlap_input.inputs(normalize=True, reshape=True, rotation=True, batch_size=cfg.batch,
                                    image_size=cfg.image_size, data_dir=args.data, fused=args.fused_input,
-                                   labels=args.labels, label_angles=args.label_angles)
+                                   labels=args.labels, label_angles=args.label_angles, pairs=args.pairs,
+                                   cross=args.cross)
+    on_epoch = None
+    if args.pairs == "mined":
+        def on_epoch(epoch):
+            if epoch % args.mine_every == 0:
+                batches.refresh_candidates(vae, k=args.mine_k)
     t0 = time.time()
-    train(vae, batches, max(args.samples_per_epoch, cfg.batch), args.epochs, driver=driver)
+    train(vae, batches, max(args.samples_per_epoch, cfg.batch), args.epochs, driver=driver, on_epoch=on_epoch)
     print(f"done in {time.time() - t0:.1f}s", file=sys.stderr)
     if args.retrieve > 0:
         retrieve_report(vae, batches, args.retrieve, shard=args.retrieve_shard or None, ranks=args.retrieve_ranks)

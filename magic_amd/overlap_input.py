@@ -43,10 +43,13 @@ def rotation_coefficients(angles, height: int, width: int) -> np.ndarray:
 
 
 def make_batch(locks: torch.Tensor, keys: torch.Tensor, idx: torch.Tensor, coef: torch.Tensor,
-               out: Optional[torch.Tensor] = None, normalize: bool = True) -> torch.Tensor:
+               out: Optional[torch.Tensor] = None, normalize: bool = True,
+               key_idx: Optional[torch.Tensor] = None) -> torch.Tensor:
     """HIP batch producer (``mvae_make_batch``): uint8 device tables [n, H, W], idx int32 [B],
     coef float32 [B, 4] -> X float32 [B, H*W*3] = per pixel (lock, rotated lock, key) / 255
-    (``normalize=False``: the raw 0..255 values, ``11a/overlap_input.py:113-115``)."""
+    (``normalize=False``: the raw 0..255 values, ``11a/overlap_input.py:113-115``). ``key_idx`` int32
+    [B] (``mvae_make_batch_x``): row b takes key ``key_idx[b]`` of a key table [m, H, W] instead of
+    key ``idx[b]``."""
     from . import _lib
     lib = _lib.load()
     n, h, w = locks.shape
@@ -55,9 +58,19 @@ def make_batch(locks: torch.Tensor, keys: torch.Tensor, idx: torch.Tensor, coef:
         if not t.is_cuda or t.dtype != dt or not t.is_contiguous():
             raise ValueError("make_batch: device tensors (uint8 tables, int32 idx, float32 coef) expected")
     out = out if out is not None else torch.empty(B, 3 * h * w, device=locks.device)
+    st = torch.cuda.current_stream(locks.device).cuda_stream
+    if key_idx is not None:
+        if not key_idx.is_cuda or key_idx.dtype != torch.int32 or not key_idx.is_contiguous() \
+                or key_idx.shape != idx.shape:
+            raise ValueError("make_batch: key_idx must be an int32 device tensor of idx's shape")
+        if keys.dim() != 3 or tuple(keys.shape[1:]) != (h, w):
+            raise ValueError("make_batch: the key table must share H and W with the lock table")
+        rc = lib.mvae_make_batch_x(locks.data_ptr(), keys.data_ptr(), h, w, idx.data_ptr(), key_idx.data_ptr(),
+                                   coef.data_ptr(), B, 255.0 if normalize else 1.0, out.data_ptr(), st)
+        _lib.check(lib, None, rc)
+        return out
     rc = lib.mvae_make_batch(locks.data_ptr(), keys.data_ptr(), h, w, idx.data_ptr(), coef.data_ptr(),
-                             B, 255.0 if normalize else 1.0, out.data_ptr(),
-                             torch.cuda.current_stream(locks.device).cuda_stream)
+                             B, 255.0 if normalize else 1.0, out.data_ptr(), st)
     _lib.check(lib, None, rc)
     return out
 
@@ -123,16 +136,29 @@ class PairBatch:
     ``coef`` float32 [B, 4] (``rotation_coefficients``). ``Engine`` and ``TangoEncoder`` take it
     wherever they take X (``mvae_*_pairs``): where the step writes its layer-0 bit operands, one
     HIP kernel reads them straight from the tables, and no [B, H*W*3] float32 array exists.
-    ``materialize()`` is that array, ``make_batch(...)``: the results are bitwise the same."""
+    ``materialize()`` is that array, ``make_batch(...)``: the results are bitwise the same.
+
+    ``key_idx`` int32 [B]: a cross-pair batch (``mvae_*_xpairs``) -- row b is lock ``idx[b]``, its
+    rotation, and key ``key_idx[b]`` of a key table [m, H, W] that only has to share H and W with
+    ``locks``. Without it the batch takes the own-pair entry points, untouched."""
 
     def __init__(self, locks: torch.Tensor, keys: torch.Tensor, idx: torch.Tensor, coef: torch.Tensor,
-                 normalize: bool = True):
+                 normalize: bool = True, key_idx: Optional[torch.Tensor] = None):
         for t, dt in ((locks, torch.uint8), (keys, torch.uint8), (idx, torch.int32), (coef, torch.float32)):
             if not t.is_cuda or t.dtype != dt or not t.is_contiguous():
                 raise ValueError("PairBatch: device tensors (uint8 tables, int32 idx, float32 coef) expected")
-        if locks.dim() != 3 or keys.shape != locks.shape or idx.dim() != 1 or coef.shape != (idx.shape[0], 4):
-            raise ValueError("PairBatch: tables [n, H, W] of one shape, idx [B], coef [B, 4] expected")
+        if key_idx is None:
+            tables = locks.dim() == 3 and keys.shape == locks.shape
+        else:
+            tables = locks.dim() == 3 and keys.dim() == 3 and keys.shape[1:] == locks.shape[1:]
+            if not key_idx.is_cuda or key_idx.dtype != torch.int32 or not key_idx.is_contiguous() \
+                    or key_idx.shape != idx.shape:
+                raise ValueError("PairBatch: key_idx must be an int32 device tensor of idx's shape")
+        if not tables or idx.dim() != 1 or coef.shape != (idx.shape[0], 4):
+            raise ValueError("PairBatch: tables [n, H, W] of one shape (with key_idx: of one H, W), idx [B], "
+                             "coef [B, 4] expected")
         self.locks, self.keys, self.idx, self.coef = locks, keys, idx, coef
+        self.key_idx = key_idx
         self.normalize = bool(normalize)
 
     @property
@@ -144,7 +170,65 @@ class PairBatch:
         return self.locks.device
 
     def materialize(self, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        return make_batch(self.locks, self.keys, self.idx, self.coef, out=out, normalize=self.normalize)
+        return make_batch(self.locks, self.keys, self.idx, self.coef, out=out, normalize=self.normalize,
+                          key_idx=self.key_idx)
+
+
+class PairLabels:
+    """The labels of the pairs a sampler draws: a lazily filled ``[n, m]`` int32 device matrix of
+    ``max_overlap`` areas over ``angles``, -1 where not yet computed. Which entries exist is kept in
+    a host bitmap, so a lookup decides what is missing without waiting for the device.
+    ``max_pairs`` bounds n*m (the default to a 256 MB matrix): a stated limit, not a measurement."""
+
+    def __init__(self, locks: torch.Tensor, keys: torch.Tensor, angles=360, max_pairs: int = 1 << 26):
+        for t in (locks, keys):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.uint8 or t.dim() != 3 \
+                    or not t.is_contiguous():
+                raise ValueError("PairLabels: contiguous uint8 device tables [n, H, W] expected")
+        if keys.shape[1:] != locks.shape[1:] or keys.device != locks.device:
+            raise ValueError("PairLabels: the tables must share H, W and the device")
+        self.n, self.m = int(locks.shape[0]), int(keys.shape[0])
+        if self.n * self.m > max_pairs:
+            raise ValueError(f"PairLabels: {self.n} x {self.m} pairs exceed max_pairs = {max_pairs}")
+        self.locks, self.keys, self.angles = locks, keys, angles
+        self.matrix = torch.full((self.n, self.m), -1, dtype=torch.int32, device=locks.device)
+        self.known = np.zeros(self.n * self.m, dtype=bool)
+        self.computed = 0  # distinct pairs labelled so far
+
+    def _compute(self, flat: np.ndarray):
+        """Label the distinct, missing pairs ``flat`` (= i*m + j, int64) with one ``max_overlap`` call."""
+        dev = self.locks.device
+        li = torch.from_numpy((flat // self.m).astype(np.int32)).to(dev)
+        ki = torch.from_numpy((flat % self.m).astype(np.int32)).to(dev)
+        areas = max_overlap(self.locks, self.keys, li, ki, angles=self.angles)[0]
+        self.matrix.view(-1)[torch.from_numpy(flat).to(dev)] = areas
+        self.known[flat] = True
+        self.computed += int(flat.size)
+
+    def lookup(self, lock_idx, key_idx) -> torch.Tensor:
+        """float32 device areas [B] of the pairs (``lock_idx[b]``, ``key_idx[b]``), host integer
+        arrays; the pairs not yet in the matrix are deduplicated and computed first."""
+        li = np.asarray(lock_idx, dtype=np.int64).reshape(-1)
+        kj = np.asarray(key_idx, dtype=np.int64).reshape(-1)
+        if li.shape != kj.shape:
+            raise ValueError("PairLabels.lookup: lock_idx and key_idx must have one length")
+        if li.size and (li.min() < 0 or li.max() >= self.n or kj.min() < 0 or kj.max() >= self.m):
+            raise ValueError("PairLabels.lookup: an index is outside its table")
+        flat = li * self.m + kj
+        miss = np.unique(flat[~self.known[flat]])
+        if miss.size:
+            self._compute(miss)
+        return self.matrix.view(-1)[torch.from_numpy(flat).to(self.matrix.device)].float()
+
+    def fill(self, chunk: int = 1 << 16) -> torch.Tensor:
+        """Compute every missing entry, at most ``chunk`` pairs per call; returns the matrix (what
+        ``retrieval.retrieve(truth=)`` takes)."""
+        if chunk < 1:
+            raise ValueError("PairLabels.fill: chunk must be at least 1")
+        miss = np.flatnonzero(~self.known)
+        for p0 in range(0, miss.size, chunk):
+            self._compute(miss[p0:p0 + chunk])
+        return self.matrix
 
 
 def random_shapes(n: int, size: int, gen: torch.Generator, device) -> torch.Tensor:
@@ -185,6 +269,20 @@ def area_distribution() -> np.ndarray:
         return np.load(_AREAS_FIXTURE).astype(np.float32)
     rng = np.random.default_rng(1)
     return np.clip(np.exp(rng.normal(7.4, 0.62, 2000)), 296, 6426).round().astype(np.float32)
+
+
+def draw_keys(rng: np.random.Generator, idx: np.ndarray, m: int, cross: float,
+              candidates: Optional[np.ndarray] = None) -> np.ndarray:
+    """The key of each row of a cross-pair batch, int64 [B]. Exactly two draws, in this order:
+    ``u = rng.random(B)``, ``kj = rng.integers(0, m, B)``. A row with ``u < cross`` takes key ``kj``
+    -- or, with ``candidates`` int [n, k] (a lock's mined keys), ``candidates[idx, kj % k]`` --
+    and every other row keeps its own key ``idx``."""
+    idx = np.asarray(idx, dtype=np.int64)
+    B = idx.shape[0]
+    u = rng.random(B)
+    kj = rng.integers(0, m, B)
+    pick = kj if candidates is None else np.asarray(candidates)[idx, kj % np.asarray(candidates).shape[1]]
+    return np.where(u < cross, pick, idx).astype(np.int64)
 
 
 def _check_labels(labels: str) -> bool:
@@ -270,13 +368,31 @@ class BatchStream:
     same draws yield ``(PairBatch, areas)`` and launch nothing; the step reads the tables.
     ``labels="sampled"`` (default): the areas are the source's, or for the synthetic pool draws from
     the reference's recorded areas, unrelated to the images. ``labels="computed"``: the area of pair
-    ``i`` of the pool is ``max_overlap`` of its lock and key over ``label_angles``, computed once here."""
+    ``i`` of the pool is ``max_overlap`` of its lock and key over ``label_angles``, computed once here.
+
+    ``pairs="own"`` (default): row b is pair ``idx[b]`` of the pool. ``"cross"``: after the draws
+    of ``"own"`` the stream draws a key of its own per row (``draw_keys``): with probability
+    ``cross`` a uniform one of the pool, else the lock's own. ``"mined"``: the same with the drawn
+    key taken from the lock's ``k`` best keys under the model as of the last
+    ``refresh_candidates(vae, k)`` (uniform before the first). Both need ``labels="computed"``: the
+    label of a row is ``max_overlap`` of its lock and its key, looked up in ``self.pair_labels``
+    (``PairLabels``), which computes the pairs it has not seen."""
 
     def __init__(self, batch: int, image_size: int, source: Optional[PairSource] = None,
                  normalize: bool = True, seed: int = 1, device="cuda", synthetic_pool: int = 960,
                  reshape: bool = True, fp16: bool = False, fused: bool = False, labels: str = "sampled",
-                 label_angles=360):
+                 label_angles=360, pairs: str = "own", cross: float = 1.0):
         computed = _check_labels(labels)
+        if pairs not in ("own", "cross", "mined"):
+            raise ValueError(f"pairs must be 'own', 'cross' or 'mined', not {pairs!r}")
+        if pairs != "own" and not computed:
+            raise ValueError(f"pairs={pairs!r} needs labels='computed': a sampled label says nothing about "
+                             "a lock and another lock's key")
+        if not 0.0 <= cross <= 1.0:
+            raise ValueError("cross must be a probability")
+        self.pairs, self.cross = pairs, float(cross)
+        self.candidates = None  # "mined": int [n, k], a lock's best keys under the model
+        self.pair_labels = None
         if fused and (not reshape or fp16):
             raise ValueError("fused=True yields a PairBatch, not an array: reshape=False and USE_FP16 "
                              "ask for the array")
@@ -302,6 +418,8 @@ class BatchStream:
         self.areas = self.areas.float().to(self.device)
         if computed:
             self.areas = max_overlap(self.locks, self.keys, angles=label_angles)[0].float()
+        if pairs != "own":
+            self.pair_labels = PairLabels(self.locks, self.keys, angles=label_angles)
         self._perm = np.empty(0, dtype=np.int64)
         self._pos = 0
 
@@ -317,6 +435,17 @@ class BatchStream:
             n -= k
         return np.concatenate(out)
 
+    def refresh_candidates(self, vae, k: int = 16, order: int = 1) -> np.ndarray:
+        """``pairs="mined"``: embed both tables with ``vae`` and keep, on the host, the ``k`` keys it
+        ranks first for every lock (``order`` +1: the largest predicted overlap first, as
+        ``retrieval.retrieve``) -- the pairs where the model claims the most overlap. Draws no
+        random number and leaves the model's training state alone."""
+        zl = vae.embed(self.locks, normalize=self.normalize)
+        zk = vae.embed(self.keys, normalize=self.normalize)
+        k = int(min(k, len(zk), 64))
+        self.candidates = np.asarray(vae.match(zl, zk, k=k, order=order)[1], dtype=np.int64)
+        return self.candidates
+
     def __iter__(self) -> Iterator:
         return self
 
@@ -325,10 +454,17 @@ class BatchStream:
         ang = self.rng.uniform(0.0, 2 * math.pi, self.batch)
         coef = torch.from_numpy(rotation_coefficients(ang, self.size, self.size)).to(self.device)
         idx_t = torch.from_numpy(idx.astype(np.int32)).to(self.device)
-        a = self.areas[idx_t.long()]
+        kidx_t = None
+        if self.pairs == "own":
+            a = self.areas[idx_t.long()]
+        else:
+            key = draw_keys(self.rng, idx, len(self.keys), self.cross,
+                            self.candidates if self.pairs == "mined" else None)
+            kidx_t = torch.from_numpy(key.astype(np.int32)).to(self.device)
+            a = self.pair_labels.lookup(idx, key)
         if self.fused:
-            return PairBatch(self.locks, self.keys, idx_t, coef, normalize=self.normalize), a
-        x = make_batch(self.locks, self.keys, idx_t, coef, normalize=self.normalize)
+            return PairBatch(self.locks, self.keys, idx_t, coef, normalize=self.normalize, key_idx=kidx_t), a
+        x = make_batch(self.locks, self.keys, idx_t, coef, normalize=self.normalize, key_idx=kidx_t)
         if not self.reshape:  # [B, H, W, 3] (11a/overlap_input.py:117-119 not applied)
             x = x.view(self.batch, self.size, self.size, 3)
         if self.fp16:  # FLAGS.USE_FP16 casts images and labels (11a/overlap_input.py:109-111)
@@ -339,12 +475,14 @@ class BatchStream:
 def inputs(normalize: bool = False, reshape: bool = False, rotation: bool = False,
            batch_size: Optional[int] = None, image_size: Optional[int] = None,
            data_dir: Optional[str] = None, device="cuda", seed: int = 1,
-           fused: bool = False, labels: str = "sampled", label_angles=360) -> BatchStream:
+           fused: bool = False, labels: str = "sampled", label_angles=360, pairs: str = "own",
+           cross: float = 1.0) -> BatchStream:
     """``11a/overlap_input.py:76-122``: images [B, H*W*3] (``reshape=True``) or [B, H, W, 3],
     divided by 255 when ``normalize``, cast to float16 with labels when ``FLAGS.USE_FP16``;
     ``rotation=False`` raises as in the reference (``:95-96``). ``fused=True`` (needs
     ``reshape=True`` and no ``USE_FP16``): images are ``PairBatch`` descriptions of the same
-    batches, which ``TangoEncoder`` takes as X. ``labels`` / ``label_angles``: see ``BatchStream``."""
+    batches, which ``TangoEncoder`` takes as X. ``labels`` / ``label_angles`` / ``pairs`` / ``cross``: see
+    ``BatchStream``."""
     if not rotation:
         raise ValueError("Rotation has to be True.")
     size = image_size or FLAGS.IMAGE_SIZE
@@ -356,4 +494,4 @@ def inputs(normalize: bool = False, reshape: bool = False, rotation: bool = Fals
         src = PairSource.from_packed(d, limit=lim) if d.endswith(".npz") else PairSource(d, limit=lim)
     return BatchStream(bs, size, src, normalize=normalize, seed=seed, device=device, reshape=reshape,
                        fp16=bool(getattr(FLAGS, "USE_FP16", False)), fused=fused, labels=labels,
-                       label_angles=label_angles)
+                       label_angles=label_angles, pairs=pairs, cross=cross)

@@ -478,7 +478,11 @@ int mvae_bench_deint(int B, int D, int variant, int iters, void* stream, float* 
  * NHWC images, B rows (3B forward images, 4B backward). mode 0: relu(conv(x, W2) + b2), 3B
  * images, y = W2 block [1601][64]; mode 1: data gradient of x (4B images), y = W2; mode 2:
  * out[2][1601][64] = the cost / metric weight gradients of x = conv2 input (3B), y = d pre-
- * activation (4B). mfma: bf16 MFMA kernels (operands rounded to bf16), else fp32 VALU.     */
+ * activation (4B). mfma bit 0: bf16 MFMA kernels (operands rounded to bf16), else fp32 VALU.
+ * Bits 1-6: the kernel forms of the create options (bit 1 conv2_half=0, 2 conv2_nw=4, 3
+ * conv2_nw=16, 4 conv2_tpb=2, 5 conv2_fpw=4, 6 conv2_wg=4). Bits 8-19: the weight gradient's
+ * chunk count (mode 2): 0 the step's defaults min(2B, 32) VALU / min(2B, 64) MFMA, else
+ * min(2B, value) for both; the slab is sized from it and prefilled with NaN bits.          */
 int mvae_debug_conv2(int S1, int B, int mode, int mfma, const float* x, const float* y, float* out,
                      void* stream);
 /* The bit operands of a batch of S x S images on caller buffers (tests; synchronous; allocates
@@ -505,6 +509,26 @@ int mvae_debug_xpairs_bits(const unsigned char* locks, const unsigned char* keys
 int mvae_debug_gemm(int M, int N, int K, const float* A, int lda, int at, const float* B, int ldb,
                     int bt, float* C, int ldc, int epi, int act, const float* aux, int ld_aux,
                     void* stream);
+/* One per-pixel kernel of the conv tower (conv_tower.hip) on caller data, through the step's own
+ * launcher (tests; synchronous; only mode 3 allocates: its slab, prefilled with NaN bits). S: image
+ * size (a multiple of 4 in 4..100), S1 = S/2, S2 = S/4; images are NHWC with 64 channels; n <= 16384.
+ *  mode 0, conv1 + ReLU + pool 1 + LRN 1 of n images: in0 = pixels [n][ld] (ld >= S S), in1 = the
+ *    conv1 block [26][64] -> out0 = p1 [n][S1 S1 64], arg_out = arg1 (same shape, bytes 0..3),
+ *    out1 = n1 fp32 and / or outb = its bf16 image (either may be NULL, not both). opt = 0.
+ *  mode 1, LRN 2 + pool 2 of n images: in0 = a2 [n][S1 S1 64] -> arg_out = arg2 [n][S2 S2 64] and
+ *    feature rows [n][ld] (ld >= S2 S2 64; columns from S2 S2 64 on are never written): out0 fp32
+ *    when opt & 1, outb = opt >> 1 (0, 1 or 3) bf16 planes [planes][n][ld].
+ *  mode 2, pool 2 + LRN 2 + ReLU backward, batch n: in0 = dxf [4n][ld], in1 = a2 [3n][S1 S1 64],
+ *    arg_in = arg2 [3n][S2 S2 64] -> out0 = da2 [4n][S1 S1 64] fp32 and / or outb = its bf16 image
+ *    (backward image j reads forward image j < 2n ? j : j - n). opt = 0.
+ *  mode 3, conv1 weight gradient, batch n: in0 = dn1 [4n][S1 S1 64], in1 = p1 [3n][S1 S1 64],
+ *    arg_in = arg1 (p1's shape), xs = pixels [3n][ld] -> out0, out1 = the cost / metric gradient
+ *    blocks [26][64]. opt: the chunk count, 0 = the step's min(2n, 1024), else min(2n, opt).
+ * Buffers a mode does not name are not touched. MVAE_EINVAL with a message, before any HIP call:
+ * another mode, S, n, ld or opt, or a NULL among the buffers the mode names.                    */
+int mvae_debug_tower(int mode, int S, int n, int ld, int opt, const float* in0, const float* in1,
+                     const float* xs, const unsigned char* arg_in, float* out0, float* out1,
+                     unsigned short* outb, unsigned char* arg_out, void* stream);
 /* The fused hidden-layer chain (enc_chain.hip) on caller data (tests; synchronous; allocates nothing).
  * x [M][ldx] bf16, layer l: w[l] [K[l]][ldw[l]] bf16 -> out[l] [M][ldo[l]] bf16. K, N, ldw, ldo, w, out are
  * HOST arrays of nl entries holding device pointers / sizes. rows: 0 auto, or 16..96 (multiple of 16).

@@ -2677,7 +2677,8 @@ extern "C" int mvae_debug_conv2(int S1, int B, int mode, int mfma, const float* 
   T.S1 = S1; T.S = 2 * S1; T.S2 = S1 / 2;
   // mfma bit 0: the MFMA kernels; the kernel form (the create options' conv2_*): bit 1 the
   // full-channel forward / data-gradient kernel, bits 2 / 3 its 4 / 16 waves, bit 4 two taps per
-  // slot, bit 5 four M-fragments per wave, bit 6 the 4-wave weight-gradient kernel
+  // slot, bit 5 four M-fragments per wave, bit 6 the 4-wave weight-gradient kernel; bits 8-19 the
+  // weight gradient's chunk count
   T.mfma = (mfma & 1) != 0;
   if (mfma & 2) T.conv2_half = false;
   if (mfma & 4) T.conv2_nw = 4;
@@ -2689,6 +2690,9 @@ extern "C" int mvae_debug_conv2(int S1, int B, int mode, int mfma, const float* 
   const int B2 = 2 * B;
   T.nchunk2 = std::min(B2, 32);
   T.nchunk2m = std::min(B2, 64);
+  // bits 8-19: the weight gradient's chunk count (0: the step's defaults above)
+  const int nchunk = (mfma >> 8) & 0xfff;
+  if (nchunk) T.nchunk2 = T.nchunk2m = std::min(B2, nchunk);
   std::vector<void*> tmp;
   hipError_t e = hipSuccess;
   auto alloc = [&](size_t bytes) -> void* {
@@ -2707,6 +2711,8 @@ extern "C" int mvae_debug_conv2(int S1, int B, int mode, int mfma, const float* 
     T.da2 = const_cast<float*>(y);
     const size_t ns = (size_t)2 * (T.mfma ? T.nchunk2m : T.nchunk2) * (25 * 64 + 1) * 64;
     T.slab = static_cast<float*>(alloc(ns * 4));
+    // every chunk writes its whole slab, the empty ones zeros: a slab left unwritten sums to NaN
+    if (e == hipSuccess) e = hipMemsetAsync(T.slab, 0xff, ns * 4, st);
     if (T.mfma) { T.n1b = bf16_of(x, 3 * B * img); T.da2b = bf16_of(y, 4 * B * img); }
     if (e == hipSuccess) e = launch_conv2_wgrad(T, B, out, out + (size_t)(25 * 64 + 1) * 64, st);
   } else {
@@ -2724,6 +2730,59 @@ extern "C" int mvae_debug_conv2(int S1, int B, int mode, int mfma, const float* 
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   for (void* p : tmp) (void)hipFree(p);
   if (e != hipSuccess) { g_create_err = hipGetErrorString(e); return (int)e; }
+  return MVAE_OK;
+}
+
+// One per-pixel kernel of the conv tower on caller buffers (tests only; synchronous): the step's
+// own launcher of conv1_fwd (mode 0), lrn2_pool2_fwd (1), pool2_bwd (2) or conv1_wgrad (3), on a
+// ConvTower whose pointers are the caller's. S: image size; include/mvae.h lists what each mode
+// reads and writes. Only mode 3 allocates (its slab, prefilled with NaN bits).
+extern "C" int mvae_debug_tower(int mode, int S, int n, int ld, int opt, const float* in0, const float* in1,
+                                const float* xs, const unsigned char* arg_in, float* out0, float* out1,
+                                unsigned short* outb, unsigned char* arg_out, void* stream) {
+  auto bad = [](const std::string& m) { return fail(nullptr, MVAE_EINVAL, "mvae_debug_tower: " + m); };
+  if (mode < 0 || mode > 3) return bad("mode must be in [0, 3]");
+  if (S < 4 || S > 100 || S % 4) return bad("S must be a multiple of 4 in [4, 100]");
+  if (n < 1 || n > 16384) return bad("n must be in [1, 16384]");
+  ConvTower T;
+  T.S = S; T.S1 = S / 2; T.S2 = S / 4;
+  const bool pixels = mode == 0 || mode == 3;   // ld strides pixel rows, else feature rows
+  if (ld < (pixels ? S * S : T.S2 * T.S2 * 64)) return bad("ld is smaller than a row");
+  hipStream_t st = (hipStream_t)stream;
+  hipError_t e = hipSuccess;
+  void* slab = nullptr;
+  if (mode == 0) {
+    if (opt) return bad("opt must be 0 in mode 0");
+    if (!in0 || !in1 || !out0 || !arg_out || (!out1 && !outb)) return bad("null buffer");
+    T.p1 = out0; T.arg1 = arg_out; T.n1 = out1; T.n1b = outb;
+    e = launch_conv1_fwd(T, in0, ld, in1, n, st);
+  } else if (mode == 1) {
+    const int f32 = opt & 1, np = opt >> 1;
+    if (opt < 0 || (np != 0 && np != 1 && np != 3) || (!f32 && !np)) return bad("opt must be f32 | planes << 1, planes 0, 1 or 3");
+    if (!in0 || !arg_out || (f32 && !out0) || (np && !outb)) return bad("null buffer");
+    T.a2 = const_cast<float*>(in0); T.arg2 = arg_out;
+    e = launch_lrn2_pool2_fwd(T, n, out0, ld, f32, Planes{np ? outb : nullptr, (long long)n * ld, np}, st);
+  } else if (mode == 2) {
+    if (opt) return bad("opt must be 0 in mode 2");
+    if (!in0 || !in1 || !arg_in || (!out0 && !outb)) return bad("null buffer");
+    T.a2 = const_cast<float*>(in1); T.arg2 = const_cast<unsigned char*>(arg_in);
+    T.da2 = out0; T.da2b = outb;
+    e = launch_pool2_bwd(T, in0, ld, n, st);
+  } else {
+    if (opt < 0 || opt > (1 << 20)) return bad("opt (the chunk count) must be in [0, 2^20]");
+    if (!in0 || !in1 || !xs || !arg_in || !out0 || !out1) return bad("null buffer");
+    T.dn1 = const_cast<float*>(in0); T.p1 = const_cast<float*>(in1);
+    T.arg1 = const_cast<unsigned char*>(arg_in);
+    T.nchunk1 = std::min(2 * n, opt ? opt : 1024);
+    const size_t ns = (size_t)2 * T.nchunk1 * 26 * 64 * sizeof(float);
+    e = hipMalloc(&slab, ns);
+    if (e == hipSuccess) e = hipMemsetAsync(slab, 0xff, ns, st);
+    T.slab = static_cast<float*>(slab);
+    if (e == hipSuccess) e = launch_conv1_wgrad(T, xs, ld, n, out0, out1, st);
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (slab) (void)hipFree(slab);
+  if (e != hipSuccess) { g_create_err = std::string("mvae_debug_tower: ") + hipGetErrorString(e); return (int)e; }
   return MVAE_OK;
 }
 

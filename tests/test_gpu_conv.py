@@ -116,35 +116,37 @@ def _bf16(a):
 
 
 def _conv2_ref(mode, x, y, S1, B):
-    """float64 restatement with the kernel's operand rounding already applied to x, y."""
+    """float64 restatement with the kernel's operand rounding already applied to x, y. The im2col
+    matrix is built one image at a time (S1 = 50 is 32 MB per image), summed in float64."""
     from oracle import conv_oracle as CV
     x = x.astype(np.float64).reshape(-1, S1, S1, 64)
     y = y.astype(np.float64)
     if mode in (0, 1):
         y = y.reshape(1601, 64)
-    if mode == 0:
-        return np.maximum(CV.conv(x, y[:1600], y[1600]), 0), CV.conv(np.abs(x), np.abs(y[:1600]), 0)
-    if mode == 1:
-        Wr = CV.rot_weights(y[:1600], 64)
-        return CV.im2col(x) @ Wr, CV.im2col(np.abs(x)) @ np.abs(Wr)
+        W, b = (y[:1600], y[1600]) if mode == 0 else (CV.rot_weights(y[:1600], 64), 0.0)
+        out, mag = np.empty_like(x), np.empty_like(x)
+        for i in range(x.shape[0]):
+            cols = CV.im2col(x[i:i + 1])
+            out[i] = cols @ W + b
+            mag[i] = np.abs(cols) @ np.abs(W)
+        return (np.maximum(out, 0) if mode == 0 else out), mag
     d = y.reshape(-1, S1, S1, 64)
-    out, mag = [], []
+    out, mag = np.zeros((2, 1601, 64)), np.zeros((2, 1601, 64))
     for g in range(2):
-        rows = np.arange(2 * B) + 2 * B * g
-        fwd = np.where(rows < 2 * B, rows, rows - B)
-        cols = CV.im2col(x[fwd]).reshape(-1, 1600)
-        dd = d[rows].reshape(-1, 64)
-        w = np.concatenate([cols.T @ dd, dd.sum(0)[None]], 0)
-        m = np.concatenate([np.abs(cols).T @ np.abs(dd), np.abs(dd).sum(0)[None]], 0)
-        out.append(w)
-        mag.append(m)
-    return np.stack(out), np.stack(mag)
+        for r in range(2 * B):
+            j = 2 * B * g + r
+            cols = CV.im2col(x[j if j < 2 * B else j - B][None]).reshape(-1, 1600)
+            dd = d[j].reshape(-1, 64)
+            out[g, :1600] += cols.T @ dd
+            out[g, 1600] += dd.sum(0)
+            mag[g, :1600] += np.abs(cols).T @ np.abs(dd)
+            mag[g, 1600] += np.abs(dd).sum(0)
+    return out, mag
 
 
-@pytest.mark.parametrize("mfma", [0, 1], ids=["valu_f32", "mfma_bf16"])
-@pytest.mark.parametrize("mode", [0, 1, 2], ids=["fwd", "dgrad", "wgrad"])
-@pytest.mark.parametrize("S1,B", [(6, 2), (10, 3), (50, 1)])
-def test_conv2_kernel(mode, mfma, S1, B, form=0):
+def _conv2_case(mode, mfma, S1, B, form=0, chunks=0, repeat=1):
+    """One mvae_debug_conv2 case against _conv2_ref: returns max|error| / max sum|terms|. With
+    repeat > 1 the later launches must equal the first bitwise."""
     from magic_amd import _lib
     lib = _lib.load()
     rng = np.random.default_rng(S1 * 10 + mode)
@@ -153,20 +155,35 @@ def test_conv2_kernel(mode, mfma, S1, B, form=0):
     x = np.maximum(rng.standard_normal(nx), -0.2).astype(np.float32)   # relu-ish, with zeros
     if mode == 2:
         y = (rng.standard_normal(4 * B * img) * (rng.random(4 * B * img) < 0.3)).astype(np.float32)
-        out = torch.zeros(2 * 1601 * 64, device="cuda")
+        nout = 2 * 1601 * 64
     else:
         y = (rng.standard_normal(1601 * 64) * 0.05).astype(np.float32)
-        out = torch.zeros((3 * B if mode == 0 else 4 * B) * img, device="cuda")
+        nout = (3 * B if mode == 0 else 4 * B) * img
     xd, yd = to_dev(x), to_dev(y)
-    rc = lib.mvae_debug_conv2(S1, B, mode, mfma | form, xd.data_ptr(), yd.data_ptr(), out.data_ptr(),
-                              torch.cuda.current_stream().cuda_stream)
-    assert rc == 0, lib.mvae_last_error(None)
+    outs = []
+    for _ in range(repeat):
+        out = torch.zeros(nout, device="cuda")
+        rc = lib.mvae_debug_conv2(S1, B, mode, mfma | form | (chunks << 8), xd.data_ptr(), yd.data_ptr(),
+                                  out.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        assert rc == 0, lib.mvae_last_error(None)
+        outs.append(out.cpu().numpy())
+    for o in outs[1:]:
+        np.testing.assert_array_equal(o.view(np.uint32), outs[0].view(np.uint32))
     xr, yr = (_bf16(x), _bf16(y)) if mfma else (x, y)
     if mfma and mode != 2:
         yr = np.concatenate([_bf16(y[:1600 * 64]), y[1600 * 64:]])   # the bias stays fp32
     ref, mag = _conv2_ref(mode, xr, yr, S1, B)
-    got = out.cpu().numpy().astype(np.float64).reshape(ref.shape)
+    got = outs[0].astype(np.float64).reshape(ref.shape)
     err = np.abs(got - ref).max() / max(np.abs(mag).max(), 1e-30)
+    print(f"conv2 mode={mode} mfma={mfma} S1={S1} B={B} form={form} chunks={chunks}: err/mag={err:.3e}")
+    return err
+
+
+@pytest.mark.parametrize("mfma", [0, 1], ids=["valu_f32", "mfma_bf16"])
+@pytest.mark.parametrize("mode", [0, 1, 2], ids=["fwd", "dgrad", "wgrad"])
+@pytest.mark.parametrize("S1,B", [(6, 2), (10, 3), (50, 1)])
+def test_conv2_kernel(mode, mfma, S1, B, form=0):
+    err = _conv2_case(mode, mfma, S1, B, form)
     assert err <= 2e-6, err
 
 
@@ -176,3 +193,93 @@ def test_conv2_kernel_full_channel_form(mode):
     option conv2_half=0; the default is the channel-half form) to the same bound."""
     test_conv2_kernel(mode, 1, 50, 1, form=2)
 
+
+@pytest.mark.parametrize("mfma", [0, 1], ids=["valu_f32", "mfma_bf16"])
+@pytest.mark.parametrize("mode", [0, 1, 2], ids=["fwd", "dgrad", "wgrad"])
+@pytest.mark.parametrize("S1,B", [(2, 2), (4, 3), (18, 1), (24, 1), (40, 1), (48, 1)])
+def test_conv2_kernel_ragged_and_tiny(mode, mfma, S1, B):
+    """Sizes whose row bands do not divide the image, and the two smallest legal images. From the
+    launchers: channel-half forward / data gradient bands hbr = min(S1, 512 // S1), weight
+    gradient row blocks R = min(S1, 256 // S1), fp32 VALU kernels 8 x 8 tiles.
+
+      S1   hbr bands      R row blocks    8 x 8 tiles
+       2   2 (whole)      2 (whole)       1, 2 of 8 rows / columns used; image < the 5 x 5 kernel, S2 = 1
+       4   4 (whole)      4 (whole)       1, 4 of 8 used; image < the 5 x 5 kernel
+      18   18 (whole)     14 + 4          3 x 3, edge tiles 2 wide
+      24   21 + 3         10 + 10 + 4     3 x 3, full
+      40   3 x 12 + 4     6 x 6 + 4       5 x 5, full
+      48   4 x 10 + 8     9 x 5 + 3       6 x 6, full
+    """
+    err = _conv2_case(mode, mfma, S1, B)
+    assert err <= 2e-6, err
+
+
+@pytest.mark.parametrize("mfma", [0, 1], ids=["valu_f32", "mfma_bf16"])
+@pytest.mark.parametrize("S1,B,chunks", [(18, 3, 2), (18, 3, 4), (50, 2, 3), (6, 5, 4)])
+def test_conv2_wgrad_chunk_loop(mfma, S1, B, chunks):
+    """Several images per weight-gradient chunk (mvae_debug_conv2 bits 8-19), ipc = ceil(2B / chunks);
+    image j of a chunk, row block b: the kernels' j0 + b / nrb, (b % nrb) * R walk.
+      (18, 3, 2): ipc 3, two ragged row blocks (14 + 4) per image;
+      (18, 3, 4): ipc 2, chunks of 2, 2, 2 images and one empty chunk;
+      (50, 2, 3): ipc 2 with 10 row blocks per image (the benchmark's loop shape: 20 row blocks per
+                  chunk, the prefetch crossing the image boundary), chunks of 2, 2, 0 images;
+      (6, 5, 4):  ipc 3, chunks of 3, 3, 3 and a last one of a single image.
+    The debug entry prefills the slab with NaN bits, so an empty chunk must write its zeros. Two
+    launches are bitwise equal (slabs are reduced in a fixed order)."""
+    err = _conv2_case(2, mfma, S1, B, chunks=chunks, repeat=2)
+    assert err <= 2e-6, err
+
+
+@pytest.mark.parametrize("mfma,S1,B", [(0, 6, 17), (1, 6, 33)], ids=["valu_f32", "mfma_bf16"])
+def test_conv2_wgrad_default_chunks_ipc2(mfma, S1, B):
+    """The step's own chunk counts past their caps: VALU nchunk2 = 32 at B = 17 (ipc 2, 17 chunks of
+    two images, 15 empty), MFMA nchunk2m = 64 at B = 33 (33 chunks of two, 31 empty)."""
+    err = _conv2_case(2, mfma, S1, B, repeat=2)
+    assert err <= 2e-6, err
+
+
+# form bits of mvae_debug_conv2 (bit 1: the full-channel kernel the other forward forms shape)
+FORMS = {"nw4": 2 | 4, "nw16": 2 | 8, "tpb2": 2 | 16, "nw4_fpw4": 2 | 4 | 32}
+
+
+@pytest.mark.parametrize("mode", [0, 1], ids=["fwd", "dgrad"])
+@pytest.mark.parametrize("form,S1", [("nw4", 50), ("nw4", 24), ("nw16", 50), ("nw16", 24), ("tpb2", 50),
+                                     ("tpb2", 40), ("nw4_fpw4", 50), ("nw4_fpw4", 40)])
+def test_conv2_kernel_forms(mode, form, S1):
+    """The full-channel kernel's other forms (create options conv2_nw=4|16, conv2_tpb=2,
+    conv2_fpw=4), at the benched size and a ragged one. Bands conv2_mfma_band = min(S1, slots // S1)
+    with slots = 32 nw fpw: nw4 256 slots (S1 = 50: 10 x 5; 24: 10 + 10 + 4), nw16 / tpb2 / nw4_fpw4
+    512 slots (50: 5 x 10; 24: 21 + 3; 40: 3 x 12 + 4)."""
+    err = _conv2_case(mode, 1, S1, 1, form=FORMS[form])
+    assert err <= 2e-6, err
+
+
+@pytest.mark.parametrize("S1,B,chunks", [(50, 1, 0), (24, 1, 0), (50, 2, 3)])
+def test_conv2_wgrad_four_wave_form(S1, B, chunks):
+    """conv2_wgrad_mfma_kernel (create option conv2_wg=4, form bit 6): the benched size, a ragged
+    one (R 10 + 10 + 4) and its image x row-block walk with ipc 2 and an empty chunk."""
+    err = _conv2_case(2, 1, S1, B, form=64, chunks=chunks, repeat=2)
+    assert err <= 2e-6, err
+
+
+# ------------------------------------------------------------------ whole steps at the new shapes
+@pytest.mark.parametrize("S", [4, 8, 36])
+def test_conv_step_f32_small_and_ragged(S):
+    """The smallest legal images (S1 = 2, 4: smaller than the 5 x 5 kernel; S2 = 1 at S = 4) and a
+    ragged one (S1 = 18) through a whole f32 step."""
+    check_step(tiny_conv("tanh", "sqdiff", True, 10.0, image_size=S, batch=3), density=0.3)
+
+
+def test_conv_step_f32_two_images_per_chunk():
+    """B = 17: the VALU weight gradient's nchunk2 = 32 < 2B, two images per chunk inside a step."""
+    check_step(tiny_conv("tanh", "sqdiff", True, 10.0, image_size=12, batch=17), density=0.3)
+
+
+@pytest.mark.parametrize("options", ["conv2_nchunk=2", "conv2_half=0"])
+def test_conv_step_bf16_options(options):
+    """bf16 at S1 = 18 (ragged weight-gradient row blocks) with three images per chunk (create option
+    conv2_nchunk=2), and with the full-channel forward / data-gradient kernel (conv2_half=0): the
+    tolerances of test_conv_step_bf16_mfma."""
+    cfg = tiny_conv("tanh", "sqdiff", True, 10.0, image_size=36, batch=3, precision="bf16", options=options)
+    check_step(cfg, density=0.3, tol=5e-2, loss_tol=2e-3, dist_tol=2e-2, adam=False,
+               g2_tol={"enc_conv2_W": 0.15, "enc_conv2_b": 0.15})

@@ -541,6 +541,60 @@ int mvae_debug_tower(int mode, int S, int n, int ld, int opt, const float* in0, 
 int mvae_debug_chain(int M, int nl, const int* K, const int* N, int act, int rows,
                      const unsigned short* x, int ldx, const unsigned short* const* w, const int* ldw,
                      unsigned short* const* out, const int* ldo, void* stream);
+/* One kernel of the latent head (mvae_kernels.hip) on caller data, through the step's own launcher
+ * (tests; synchronous; allocates nothing). Every pointer is a device pointer; a buffer the mode does
+ * not name is not read (it may be NULL). B rows of this rank, L latent columns, global batch Bg
+ * (inv_bg = 1 / Bg as the step forms it). Stacked rows are [rot | lock | key].
+ *  eps source (modes FWD and BWD): eps [3][B][L] in the reference's slot order (lock, rot, key), or
+ *    NULL: the Philox stream (seed, counter) at this rank's rows off .. off + B - 1 of Bg.
+ *  MVAE_HEAD_FWD: ms [3B][2L] -> rowfwd [B][4]; z [3B][ldz] fp32 lock rows when zmask & 2, key rows
+ *    when zmask & 4 (zmask in {0, 2, 4, 6}); z_planes (0, 1 or 3) bf16 planes of the lock rows into
+ *    zp [z_planes][3B][ldz]. Rot rows, pad columns and unselected rows are never written.
+ *  MVAE_HEAD_COLSTATS: cs_mode 0, out [2L] = column sums of squares of z's lock | key rows; cs_mode 1,
+ *    out [L] = coldot from z, colsq [2L] and draw [B]. part: colstats_nchunk(B) = ceil(B / 128) rows
+ *    of 2L (cs_mode 0) or L floats. cnt: NULL (two launches), or ceil(ncols / 64) zeroed ints (one
+ *    launch; left zeroed).
+ *  MVAE_HEAD_METRIC: z, rowfwd, rowpart [B][nblk], areas [B] or NULL (zeros), colsq (cosine only);
+ *    metric 0 cosine / 1 sqdiff, recip, w -> rowvals [B][4], dist [B], draw [B].
+ *  MVAE_HEAD_LOSS: rowvals [B][4] -> losses[0..4].
+ *  MVAE_HEAD_BWD: ms, eps source, dzdec [B][L], draw [B], and for the cosine colsq [2L], coldot [L];
+ *    metric, w -> dhead [4B][ldh] fp32 (or NULL) and h_planes (0, 1 or 3) bf16 planes
+ *    hp [h_planes][4B][ldh]; columns from 2L on are never written.
+ * MVAE_EINVAL with a message, before any HIP call: args NULL, another mode, B < 1, L < 1, Bg < B, a
+ * stride smaller than the row (ldz < L, ldh < 2L), a bad zmask / plane count / cs_mode / metric /
+ * nblk, off outside [0, Bg - B] with regenerated eps, a NULL among the buffers the mode names,
+ * neither dhead nor planes in MVAE_HEAD_BWD, or a pointer that is not 16-byte aligned where the
+ * kernel's 16-byte form is chosen (L % 4 == 0 with ldz % 4 == 0, resp. ldh % 4 == 0; rowfwd and
+ * rowvals always).                                                                              */
+enum { MVAE_HEAD_FWD = 0, MVAE_HEAD_COLSTATS = 1, MVAE_HEAD_METRIC = 2, MVAE_HEAD_LOSS = 3, MVAE_HEAD_BWD = 4 };
+typedef struct mvae_head_args {
+  int mode, B, L, Bg, ldz, ldh;
+  int off;                          /* regenerated eps: this rank's first row */
+  int zmask, z_planes, h_planes;
+  int cs_mode, nblk, metric, recip;
+  float w;                          /* deformation weight */
+  unsigned long long seed, counter; /* regenerated eps */
+  const float* ms;
+  const float* eps;
+  const float* areas;
+  const float* rowpart;
+  const float* dzdec;
+  float* z;
+  unsigned short* zp;
+  float* rowfwd;
+  float* colsq;
+  float* coldot;
+  float* draw;
+  float* part;
+  int* cnt;
+  float* out;
+  float* rowvals;
+  float* dist;
+  float* losses;
+  float* dhead;
+  unsigned short* hp;
+} mvae_head_args;
+int mvae_debug_head(const mvae_head_args* args, void* stream);
 
 #ifdef __cplusplus
 }

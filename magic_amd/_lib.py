@@ -70,6 +70,23 @@ class mvae_match_opts(C.Structure):
                 ("dist_ld", C.c_int64), ("thr_val", C.c_void_p), ("thr_idx", C.c_void_p), ("ahead", C.c_void_p)]
 
 
+HEAD_FWD, HEAD_COLSTATS, HEAD_METRIC, HEAD_LOSS, HEAD_BWD = range(5)
+
+
+class mvae_head_args(C.Structure):
+    """Arguments of ``mvae_debug_head`` (``include/mvae.h``): sizes and device pointers; a zeroed
+    field is a NULL / 0 argument."""
+    _fields_ = [("mode", C.c_int), ("B", C.c_int), ("L", C.c_int), ("Bg", C.c_int), ("ldz", C.c_int),
+                ("ldh", C.c_int), ("off", C.c_int), ("zmask", C.c_int), ("z_planes", C.c_int),
+                ("h_planes", C.c_int), ("cs_mode", C.c_int), ("nblk", C.c_int), ("metric", C.c_int),
+                ("recip", C.c_int), ("w", C.c_float), ("seed", C.c_uint64), ("counter", C.c_uint64),
+                ("ms", C.c_void_p), ("eps", C.c_void_p), ("areas", C.c_void_p), ("rowpart", C.c_void_p),
+                ("dzdec", C.c_void_p), ("z", C.c_void_p), ("zp", C.c_void_p), ("rowfwd", C.c_void_p),
+                ("colsq", C.c_void_p), ("coldot", C.c_void_p), ("draw", C.c_void_p), ("part", C.c_void_p),
+                ("cnt", C.c_void_p), ("out", C.c_void_p), ("rowvals", C.c_void_p), ("dist", C.c_void_p),
+                ("losses", C.c_void_p), ("dhead", C.c_void_p), ("hp", C.c_void_p)]
+
+
 class mvae_tensor(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("data", C.c_void_p), ("rows", C.c_int),
                 ("cols", C.c_int), ("ld", C.c_int), ("trained_by", C.c_int)]
@@ -168,6 +185,7 @@ _SIGS = {
     "mvae_debug_chain": ([C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int,
                           C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int),
                           C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_void_p], C.c_int),
+    "mvae_debug_head": ([C.POINTER(mvae_head_args), C.c_void_p], C.c_int),
 }
 
 EXPORTED = tuple(_SIGS)

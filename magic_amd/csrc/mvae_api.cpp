@@ -2890,3 +2890,77 @@ extern "C" int mvae_debug_chain(int M, int nl, const int* K, const int* N, int a
   if (e != hipSuccess) { g_create_err = std::string("mvae_debug_chain: ") + hipGetErrorString(e); return (int)e; }
   return MVAE_OK;
 }
+
+// One kernel of the latent head on caller buffers (tests only; synchronous; allocates nothing): the
+// step's own launcher of latent_fwd, colstats, metric, loss_reduce or latent_bwd, with the plane
+// strides the step uses (the whole fp32 buffer: 3B ldz resp. 4B ldh elements). Everything the
+// kernels' addressing relies on is checked here, before any HIP call; include/mvae.h lists what
+// each mode reads and writes.
+extern "C" int mvae_debug_head(const mvae_head_args* args, void* stream) {
+  auto bad = [](const std::string& m) { return fail(nullptr, MVAE_EINVAL, "mvae_debug_head: " + m); };
+  auto misaligned = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
+  if (!args) return bad("args is NULL");
+  const mvae_head_args& a = *args;
+  if (a.mode < MVAE_HEAD_FWD || a.mode > MVAE_HEAD_BWD) return bad("mode must be in [0, 4]");
+  if (a.B < 1 || a.L < 1) return bad("B and L must be at least 1");
+  if (a.B > (1 << 24) || a.L > (1 << 20)) return bad("B or L too large");
+  if (a.Bg < a.B) return bad("Bg must be at least B");
+  const int B = a.B, L = a.L;
+  const float inv_bg = 1.f / (float)a.Bg;
+  const bool uses_z = a.mode == MVAE_HEAD_FWD || a.mode == MVAE_HEAD_COLSTATS || a.mode == MVAE_HEAD_METRIC;
+  if (uses_z && a.ldz < L) return bad("ldz is smaller than a row");
+  if (a.mode == MVAE_HEAD_BWD && a.ldh < 2 * L) return bad("ldh is smaller than a row");
+  LatentEps le;
+  if (a.mode == MVAE_HEAD_FWD || a.mode == MVAE_HEAD_BWD) {
+    if (!a.ms) return bad("ms is NULL");
+    le.buf = a.eps; le.seed = a.seed; le.counter = a.counter; le.Bg = a.Bg; le.off = a.off;
+    if (!a.eps && (a.off < 0 || a.off > a.Bg - B)) return bad("off outside [0, Bg - B]");
+  }
+  hipStream_t st = (hipStream_t)stream;
+  hipError_t e = hipSuccess;
+  if (a.mode == MVAE_HEAD_FWD) {
+    const int np = a.z_planes;
+    if (a.zmask & ~6) return bad("zmask must be 0, 2, 4 or 6");
+    if (np != 0 && np != 1 && np != 3) return bad("z_planes must be 0, 1 or 3");
+    if (!a.rowfwd || (a.zmask && !a.z) || (np && !a.zp)) return bad("null buffer");
+    if (misaligned(a.rowfwd)) return bad("rowfwd is not 16-byte aligned");
+    if (L % 4 == 0 && a.ldz % 4 == 0 &&
+        (misaligned(a.ms) || misaligned(a.eps) || (a.zmask && misaligned(a.z)) || (np && misaligned(a.zp))))
+      return bad("ms, eps, z or zp is not 16-byte aligned");
+    e = launch_latent_fwd(a.ms, le, a.z, Planes{np ? a.zp : nullptr, (long long)3 * B * a.ldz, np}, a.zmask, B, L,
+                          a.ldz, a.rowfwd, st);
+  } else if (a.mode == MVAE_HEAD_COLSTATS) {
+    if (a.cs_mode != 0 && a.cs_mode != 1) return bad("cs_mode must be 0 or 1");
+    if (!a.z || !a.part || !a.out || (a.cs_mode == 1 && (!a.colsq || !a.draw))) return bad("null buffer");
+    e = launch_colstats(a.cs_mode, a.z, B, L, a.ldz, a.colsq, a.draw, a.part, colstats_nchunk(B), a.out, st, a.cnt);
+  } else if (a.mode == MVAE_HEAD_METRIC) {
+    if (a.metric != 0 && a.metric != 1) return bad("metric must be 0 (cosine) or 1 (sqdiff)");
+    if (a.nblk < 0) return bad("nblk must not be negative");
+    if (!a.z || !a.rowfwd || (a.nblk && !a.rowpart) || (a.metric == 0 && !a.colsq) || !a.rowvals || !a.dist ||
+        !a.draw)
+      return bad("null buffer");
+    if (misaligned(a.rowfwd)) return bad("rowfwd is not 16-byte aligned");
+    if (a.metric == 0 && L % 4 == 0 && L >= 64 && a.ldz % 4 == 0 && misaligned(a.z))
+      return bad("z is not 16-byte aligned");
+    e = launch_metric(a.z, a.ldz, a.rowfwd, a.rowpart, a.nblk, a.areas, a.colsq, B, L, a.metric, a.recip != 0, a.w,
+                      inv_bg, a.rowvals, a.dist, a.draw, st);
+  } else if (a.mode == MVAE_HEAD_LOSS) {
+    if (!a.rowvals || !a.losses) return bad("null buffer");
+    if (misaligned(a.rowvals)) return bad("rowvals is not 16-byte aligned");
+    e = launch_loss_reduce(a.rowvals, B, inv_bg, a.losses, st);
+  } else {
+    const int np = a.h_planes;
+    if (a.metric != 0 && a.metric != 1) return bad("metric must be 0 (cosine) or 1 (sqdiff)");
+    if (np != 0 && np != 1 && np != 3) return bad("h_planes must be 0, 1 or 3");
+    if (!a.dhead && !np) return bad("neither dhead nor planes to write");
+    if (!a.dzdec || !a.draw || (a.metric == 0 && (!a.colsq || !a.coldot)) || (np && !a.hp)) return bad("null buffer");
+    if (L % 4 == 0 && a.ldh % 4 == 0 &&
+        (misaligned(a.ms) || misaligned(a.eps) || misaligned(a.dzdec) || misaligned(a.dhead) || (np && misaligned(a.hp))))
+      return bad("ms, eps, dzdec, dhead or hp is not 16-byte aligned");
+    e = launch_latent_bwd(a.ms, le, a.dzdec, a.draw, a.colsq, a.coldot, B, L, a.metric, a.w, inv_bg, a.dhead, a.ldh,
+                          Planes{np ? a.hp : nullptr, (long long)4 * B * a.ldh, np}, st);
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) { g_create_err = std::string("mvae_debug_head: ") + hipGetErrorString(e); return (int)e; }
+  return MVAE_OK;
+}

@@ -1,0 +1,688 @@
+// libmvae: the diagnostics entry points (debug_* for the tests, bench_* for kernel timing). They
+// run the step's own launchers on caller data or on operands made here, need no context, and
+// report through mvae_last_error(NULL). Device memory and events of one call live in an Arena.
+#include "mvae_ctx.h"
+
+namespace {
+
+// device buffers and events of one diagnostics call, released when it returns
+struct Arena {
+  hipStream_t st;
+  hipError_t err = hipSuccess;  // the first failure; later requests then return null at once
+  std::vector<void*> ptrs;
+  std::vector<hipEvent_t> events;
+  explicit Arena(hipStream_t s) : st(s) {}
+  ~Arena() {
+    for (hipEvent_t e : events) (void)hipEventDestroy(e);
+    for (void* p : ptrs) (void)hipFree(p);
+  }
+  // count elements of T; zero: cleared on the stream. Check err (DIAG(ar.err)) before use
+  template <class T>
+  T* alloc(size_t count, bool zero = false) {
+    const size_t bytes = std::max<size_t>(count * sizeof(T), 4);
+    void* q = nullptr;
+    if (err == hipSuccess && (err = hipMalloc(&q, bytes)) == hipSuccess) ptrs.push_back(q);
+    if (q && zero) err = hipMemsetAsync(q, 0, bytes, st);
+    return static_cast<T*>(q);
+  }
+  hipEvent_t event() {
+    hipEvent_t ev = nullptr;
+    if (err == hipSuccess && (err = hipEventCreate(&ev)) == hipSuccess) events.push_back(ev);
+    return ev;
+  }
+};
+
+// early return with the error string stored (`who`: the caller's prefix, in scope)
+#define DIAG(expr) MV_TRY(nullptr, who, expr)
+bool misaligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
+
+// mvae_bench_gemm's epilogue (variant >> 8): the step's fused epilogues with their operand reads
+// and the output planes the next GEMM would read (np planes of nc elements)
+int bench_epilogue(Arena& ar, GemmDesc& d, int epi, int np, size_t nc) {
+  const char* who = "";
+  hipStream_t st = ar.st;
+  const int M = d.M, N = d.N, ldc = d.ldc;
+  if (epi > EPI_SIGMOID) DIAG(hipErrorInvalidValue);
+  d.epi.mode = epi;
+  d.epi.act = ACT_TANH;
+  float* aux = ar.alloc<float>((size_t)M * ldc);
+  DIAG(ar.err);
+  DIAG(launch_normal(aux, 1, 1, M * ldc, 1, 0, 3, 0, st));
+  float* rowpart = epi == EPI_BCE ? ar.alloc<float>((size_t)M * gemm_bce_nblk(N)) : nullptr;
+  d.epi.aux = aux; d.epi.ld_aux = ldc;
+  d.epi.x = aux; d.epi.ldx = ldc;
+  d.epi.rowpart = rowpart;
+  d.epi.scale = 1.f / M;
+  if (epi == EPI_ACT || epi == EPI_DACT) d.epi.padw = 1;  // as the step's padded rows
+  if (!np) return MVAE_OK;
+  d.epi.cp = ar.alloc<unsigned short>((size_t)np * nc); d.epi.pc = (long long)nc; d.epi.ncp = np;
+  // MVAE_BENCH_PLANES_ONLY=1: the output as planes only, as the step's producers write it;
+  // the BCE head as in the step: binary targets read from their bf16 plane (EPI_BCEB)
+  if (const char* po = std::getenv("MVAE_BENCH_PLANES_ONLY"); po && *po == '1') {
+    d.epi.c32 = 0;
+    if (epi == EPI_BCE) {
+      const size_t nx = (size_t)M * ldc;
+      DIAG(launch_binarize(aux, nx, st));
+      auto* xpl = ar.alloc<unsigned short>(nx + 8);  // (+ 16 B: the zeroed flag words behind the plane)
+      DIAG(ar.err);
+      DIAG(launch_split_planes(aux, nx, Planes{xpl, 0, 1}, st));
+      DIAG(hipMemsetAsync(xpl + nx, 0, 16, st));
+      d.epi.xp = xpl;
+      d.epi.xdyn = reinterpret_cast<const int*>(xpl + nx);
+      d.epi.xnb = d.epi.xdyn + 2;  // (the zeroed 16 B: binarized targets)
+    }
+  }
+  return MVAE_OK;
+}
+
+// one more launch of d with a zeroed stamp buffer of `words` words, copied to h
+int stamped_launch(const GemmDesc& d, float* ws, size_t ws_n, hipStream_t st, size_t words,
+                   std::vector<unsigned long long>* h) {
+  const char* who = "";
+  Arena ar(st);
+  auto* sb = ar.alloc<unsigned long long>(words, true);
+  DIAG(ar.err);
+  GemmDesc ds = d;
+  ds.stamps = sb;
+  DIAG(gemm_run(ds, ws, ws_n, st));
+  DIAG(hipStreamSynchronize(st));
+  h->resize(words);
+  DIAG(hipMemcpy(h->data(), sb, words * 8, hipMemcpyDeviceToHost));
+  return MVAE_OK;
+}
+
+// MVAE_STAMPS=1: the stamped ring-kernel build's per-workgroup segment times (us, 100 MHz stamps)
+void print_ring_stamps(const std::vector<unsigned long long>& h, int nmax, int M, int N, int K) {
+  int n = 0, niss = 0;
+  unsigned long long lo = ~0ull, hi = 0;
+  double seg[3] = {0, 0, 0}, iss = 0, wsum = 0, vsum = 0;
+  std::vector<unsigned long long> st0s, ends;  // every workgroup's first and last stamp
+  for (int i = 0; i < nmax; ++i) {
+    const unsigned long long* q = &h[8 * (size_t)i];
+    if (!q[0]) continue;
+    ++n;
+    lo = std::min(lo, q[0]); hi = std::max(hi, q[3]);
+    st0s.push_back(q[0]); ends.push_back(q[3]);
+    for (int k = 0; k < 3; ++k) seg[k] += (double)(q[k + 1] - q[k]) * 0.01;
+    if (q[4]) { iss += (double)(q[4] - q[2]) * 0.01; ++niss; }
+    wsum += (double)q[5] * 0.01;
+    vsum += (double)q[6] * 0.01;
+  }
+  if (niss) std::fprintf(stderr, "[stamps] epilogue stores issued after %.2f us (mean of %d WGs)\n", iss / niss, niss);
+  if (!n) return;
+  std::fprintf(stderr, "[stamps] k-loop iteration boundaries (wave 0): vmcnt wait %.2f us, barrier %.2f us per WG\n", vsum / n, wsum / n);
+  std::sort(st0s.begin(), st0s.end());
+  std::sort(ends.begin(), ends.end());
+  auto us = [&](unsigned long long t) { return (t - lo) * 0.01; };
+  std::fprintf(stderr, "[stamps] M %d N %d K %d: %d workgroups, span %.2f us; mean per WG: prologue %.2f, "
+               "k-loop %.2f, epilogue %.2f us; start p50/p90/max %.2f/%.2f/%.2f; end p10/p50/max %.2f/%.2f/%.2f\n",
+               M, N, K, n, (hi - lo) * 0.01, seg[0] / n, seg[1] / n, seg[2] / n,
+               us(st0s[n / 2]), us(st0s[n * 9 / 10]), us(st0s[n - 1]), us(ends[n / 10]), us(ends[n / 2]), us(ends[n - 1]));
+}
+
+// MVAE_STAMPS=2: the stamped eight-phase build (EPI_STORE, C/D epilogue): per wave the shader
+// cycles of each of a k-tile's 8 barrier-delimited slots, summed over its k-loop; printed per
+// k-tile for waves 0-3 and 4-7 (the half one barrier behind), with the in-kernel clock (shader
+// cycles / 100 MHz realtime)
+void print_e8_stamps(const std::vector<unsigned long long>& h, size_t nwaves, int M, int N, int K) {
+  double slot[2][8] = {}, tot[2] = {}, tiles[2] = {}, cyc = 0, rt = 0, pro = 0, loop_us = 0, epi = 0;
+  int nw = 0;
+  for (size_t w = 0; w < nwaves; ++w) {
+    const unsigned long long* q = &h[16 * w];
+    if (!q[10]) continue;
+    const int half = (int)(w % 8) / 4;
+    for (int k = 0; k < 8; ++k) slot[half][k] += (double)q[k];
+    tot[half] += (double)q[8];
+    tiles[half] += (double)q[10];
+    cyc += (double)q[8];
+    rt += (double)q[9];
+    pro += (double)q[11] * 0.01;
+    loop_us += (double)q[9] * 0.01;
+    epi += (double)q[12] * 0.01;
+    ++nw;
+  }
+  if (!nw) return;
+  std::fprintf(stderr, "[e8stamps] M %d N %d K %d: %d waves, clock %.3f GHz, k-loop cycles per k-tile: "
+               "waves0-3 %.0f, waves4-7 %.0f; per workgroup: prologue %.2f us, k-loop %.2f us, epilogue %.2f us\n",
+               M, N, K, nw, cyc / rt * 0.1, tot[0] / tiles[0], tot[1] / tiles[1], pro / nw, loop_us / nw, epi / nw);
+  for (int hf = 0; hf < 2; ++hf) {
+    std::fprintf(stderr, "[e8stamps]   waves%s slots per k-tile:", hf ? "4-7" : "0-3");
+    for (int k = 0; k < 8; ++k) std::fprintf(stderr, " %.0f", slot[hf][k] / tiles[hf]);
+    std::fprintf(stderr, "\n");
+  }
+}
+
+}  // namespace
+
+extern "C" int mvae_debug_gemm(int M, int N, int K, const float* A, int lda, int at, const float* Bm,
+                               int ldb, int bt, float* Cm, int ldc, int epi, int act, const float* aux,
+                               int ld_aux, void* stream) {
+  if ((epi & 15) == EPI_BCE || epi < 0 || (epi & 15) > EPI_SIGMOID || ((epi >> 4) & 15) > 2)
+    return fail(nullptr, MVAE_EINVAL, "bad epilogue");
+  const char* who = "";
+  hipStream_t st = (hipStream_t)stream;
+  Arena ar(st);
+  GemmDesc d = gd(M, N, K, A, lda, at != 0, Bm, ldb, bt != 0, Cm, ldc, epi & 15);
+  d.prec = (epi >> 4) & 15;  // 0 fp32, 1 bf16, 2 fp32-accurate bf16 split
+  d.variant = (epi >> 8) & 15;
+  if (d.variant == 9) { d.valu = 1; d.prec = GEMM_F32; d.variant = 0; }  // the fp32 VALU kernel
+  if ((epi >> 13) & 1) d.tm = 192;  // epi bit 13: the ring kernel's 192-row tiles where eligible
+  d.x3 = (epi >> 16) & 3;           // epi bits 16-17: f32x ring plans on the plane-stacked kernels (x3 option)
+  d.epi.act = act;
+  d.epi.aux = aux;
+  d.epi.ld_aux = ld_aux;
+  const int np = d.prec == GEMM_BF16 ? 1 : 3;  // (plane modes)
+  if (d.prec != GEMM_F32) {  // plane images of the operands (the step's producers write these)
+    const size_t na = (size_t)(at ? K : M) * lda, nb = (size_t)(bt ? N : K) * ldb;
+    Planes A_{ar.alloc<unsigned short>(np * na), (long long)na, np};
+    Planes B_{ar.alloc<unsigned short>(np * nb), (long long)nb, np};
+    DIAG(ar.err);
+    DIAG(launch_split_planes(A, na, A_, st));
+    DIAG(launch_split_planes(Bm, nb, B_, st));
+    d.Ap = A_.p; d.pA = A_.stride; d.nA = np;
+    d.Bp = B_.p; d.pB = B_.stride; d.nB = np;
+  }
+  // epi bit 14 (plane modes, A of 0/1 values): A also as a BitMat, the eight-phase kernel's bits path
+  if (((epi >> 14) & 1) && d.prec != GEMM_F32) {
+    const int kts = bitmat_kts(K);
+    auto* pbits = ar.alloc<unsigned>(bitmat_words(M, K));
+    auto* pnb = ar.alloc<int>(4, true);
+    DIAG(ar.err);
+    DIAG(launch_bits_from_plane(d.Ap, lda, at != 0, M, K, pbits, kts, pnb, st));
+    d.Abits = pbits; d.abits_kts = kts; d.anb = pnb;
+    d.bits_reg = (epi >> 15) & 1;  // epi bit 15: its words loaded to registers (E8 BITS 2)
+  }
+  // epi bit 12 (plane modes): the output as bf16 planes only (no fp32 store), as the step's
+  // producers write their operand images; C then receives the planes' sum (host side)
+  const bool planes_out = ((epi >> 12) & 1) && d.prec != GEMM_F32;
+  const size_t nc = (size_t)M * ldc;
+  unsigned short* cpl = planes_out ? ar.alloc<unsigned short>(np * nc, true) : nullptr;
+  if (planes_out) { d.epi.cp = cpl; d.epi.pc = (long long)nc; d.epi.ncp = np; d.epi.c32 = 0; }
+  const size_t ws_n = gemm_workspace_elems(d);
+  float* ws = ws_n ? ar.alloc<float>(ws_n) : nullptr;
+  DIAG(ar.err);
+  DIAG(gemm_run(d, ws, ws_n, st));
+  DIAG(hipStreamSynchronize(st));
+  if (planes_out) {
+    std::vector<unsigned short> h(np * nc);
+    std::vector<float> c(nc);
+    DIAG(hipMemcpy(h.data(), cpl, h.size() * 2, hipMemcpyDeviceToHost));
+    DIAG(hipMemcpy(c.data(), Cm, nc * 4, hipMemcpyDeviceToHost));
+    for (int r = 0; r < M; ++r)
+      for (int j = 0; j < N; ++j) {
+        const size_t o = (size_t)r * ldc + j;
+        float v = 0.f;
+        for (int t = np - 1; t >= 0; --t) {
+          uint32_t u = (uint32_t)h[t * nc + o] << 16;
+          float f;
+          std::memcpy(&f, &u, 4);
+          v += f;
+        }
+        c[o] = v;
+      }
+    DIAG(hipMemcpy(Cm, c.data(), nc * 4, hipMemcpyHostToDevice));
+  }
+  return MVAE_OK;
+}
+
+// (diagnostics) the de-interleave of a [B][3D] batch of random 0/1 pixels (half of them 1), iters
+// launches on the stream: variant 0 the step's bits form (launch_deint_bits), 7 the same without
+// the weight-gradient words (no_xbw), 100 the bf16-plane pass; any other variant is MVAE_EINVAL
+extern "C" int mvae_bench_deint(int B, int D, int variant, int iters, void* stream, float* avg_ms) {
+  if (B <= 0 || D <= 0 || B % 64 || D % 8 || iters <= 0 || !avg_ms || variant < 0) return MVAE_EINVAL;
+  {
+    const int form = variant % 2000 % 1000;  // (the modifiers below taken off)
+    if (form != 0 && form != 7 && form != 100) return MVAE_EINVAL;
+  }
+  const char* who = "";
+  hipStream_t st = (hipStream_t)stream;
+  Arena ar(st);
+  const int ldx = (D + 1 + 7) / 8 * 8, ldbits = (D / 8 + 15) & ~15;
+  const int kf = bitmat_kts(D + 1), kw = bitmat_kts(3 * B);
+  // variant + 1000: four X images in turn (none of the next launch's X left in the 256 MB
+  // last-level cache, as in the step, where the rest of the step's traffic evicts it)
+  // variant + 2000 / + 4000: before every timed launch (each timed alone by its own events) a
+  // heater -- a bf16 8192^3 GEMM (~1 ms of MFMA load, as the step's layer-0 weight gradient
+  // precedes the next step's pass) / a 1 GB device memset (dirty lines)
+  const int heat = variant >= 4000 ? 2 : (variant >= 2000 ? 1 : 0);
+  variant %= 2000;
+  const int nx = variant >= 1000 ? 4 : 1;
+  variant %= 1000;
+  float* xr[4] = {nullptr, nullptr, nullptr, nullptr};
+  for (int i = 0; i < nx; ++i) xr[i] = ar.alloc<float>((size_t)B * 3 * D, true);
+  float* x = xr[0];
+  auto* xs = ar.alloc<float>((size_t)3 * B * ldx, true);
+  auto* xp = ar.alloc<unsigned short>((size_t)3 * B * ldx, true);
+  auto* xbf = ar.alloc<unsigned>(bitmat_words(3 * B, D + 1), true);
+  auto* xbw = ar.alloc<unsigned>(bitmat_words(D + 1, 3 * B), true);
+  auto* xb = ar.alloc<unsigned char>((size_t)B * ldbits, true);
+  auto* dyn = ar.alloc<int>(16, true);
+  DIAG(ar.err);
+  for (int i = 0; i < nx; ++i) {
+    DIAG(launch_normal(xr[i], 1, 1, B * 3 * D, 1, 0, 5 + i, 0, st));
+    DIAG(launch_binarize(xr[i], (size_t)B * 3 * D, st));  // x > 0: half the pixels 1
+  }
+  int it = 0;
+  const Planes pl{xp, (long long)3 * B * ldx, 1};
+  auto one = [&]() -> hipError_t {
+    x = xr[it++ % nx];
+    if (variant == 100) return launch_deinterleave(x, xs, pl, dyn, dyn + 4, B, D, ldx, 0, 2, st, xb, ldbits);
+    return launch_deint_bits(x, B, D, xbf, kf, xbw, kw, xb, ldbits, dyn, dyn + 4, xs, pl, ldx, 2, variant == 7, st);
+  };
+  hipEvent_t t0 = ar.event(), t1 = ar.event();
+  DIAG(ar.err);
+  for (int i = 0; i < 3; ++i) DIAG(one());
+  float ms = 0.f;
+  if (heat) {
+    const int G = 8192;
+    auto* ga = ar.alloc<unsigned short>((size_t)G * G, true);
+    auto* gb = ar.alloc<unsigned short>((size_t)G * G, true);
+    auto* gc = ar.alloc<float>((size_t)G * G, true);
+    char* junk = heat == 2 ? ar.alloc<char>((size_t)1 << 30, true) : nullptr;
+    DIAG(ar.err);
+    // random operands (a GEMM on zeros draws less power and holds a higher clock)
+    DIAG(launch_normal(gc, 1, 1, G * G, 1, 0, 11, 0, st));
+    DIAG(launch_split_planes(gc, (size_t)G * G, Planes{ga, (long long)G * G, 1}, st));
+    DIAG(launch_normal(gc, 1, 1, G * G, 1, 0, 12, 0, st));
+    DIAG(launch_split_planes(gc, (size_t)G * G, Planes{gb, (long long)G * G, 1}, st));
+    GemmDesc d = gd(G, G, G, nullptr, G, false, nullptr, G, false, gc, G);
+    d.prec = GEMM_BF16; d.Ap = ga; d.pA = (long long)G * G; d.nA = 1; d.Bp = gb; d.pB = (long long)G * G; d.nB = 1;
+    for (int i = 0; i < iters; ++i) {
+      DIAG(heat == 1 ? gemm_run(d, nullptr, 0, st) : hipMemsetAsync(junk, i & 0xff, (size_t)1 << 30, st));
+      DIAG(hipEventRecord(t0, st));
+      DIAG(one());
+      DIAG(hipEventRecord(t1, st));
+      DIAG(hipEventSynchronize(t1));
+      float m1 = 0.f;
+      DIAG(hipEventElapsedTime(&m1, t0, t1));
+      ms += m1;
+    }
+  } else {
+    DIAG(hipEventRecord(t0, st));
+    for (int i = 0; i < iters; ++i) DIAG(one());
+    DIAG(hipEventRecord(t1, st));
+    DIAG(hipEventSynchronize(t1));
+    DIAG(hipEventElapsedTime(&ms, t0, t1));
+  }
+  *avg_ms = ms / iters;
+  return MVAE_OK;
+}
+
+// Time one GEMM shape of the step's kernel family (diagnostics): operands are allocated
+// and filled with uniform [-1,1) values inside, `iters` launches are timed with HIP events
+// on `stream` after 3 warm-ups. variant selects a kernel variant (0 = default).
+extern "C" int mvae_bench_gemm(int M, int N, int K, int at, int bt, int batch, int variant, int iters,
+                               void* stream, float* avg_ms) {
+  if (M <= 0 || N <= 0 || K <= 0 || iters <= 0 || !avg_ms || batch <= 0) return MVAE_EINVAL;
+  const char* who = "";
+  hipStream_t st = (hipStream_t)stream;
+  Arena ar(st);
+  // operand rows padded to 8 elements (16 B), as the step's buffers are
+  // MVAE_BENCH_LDPAD (diagnostics): row strides rounded to this many elements (default 8)
+  int pad = 8;
+  if (const char* lp = std::getenv("MVAE_BENCH_LDPAD"); lp && std::atoi(lp) >= 8) pad = std::atoi(lp) & ~7;
+  auto rnd = [&](int v) { return (v + pad - 1) / pad * pad; };
+  const int lda = rnd(at ? M : K), ldb = rnd(bt ? K : N);
+  const size_t sa = (size_t)(at ? K : M) * lda, sb = (size_t)(bt ? N : K) * ldb;
+  const int ldc = rnd(N);  // output rows padded to 16 B as well (the 16-B epilogue stores)
+  const size_t na = sa * batch, nb = sb * batch, nc = (size_t)M * ldc * batch;
+  GemmDesc d = gd(M, N, K, nullptr, lda, at != 0, nullptr, ldb, bt != 0, nullptr, ldc);
+  d.batch = batch; d.sA = (long long)sa; d.sB = (long long)sb; d.sC = (long long)M * ldc;
+  d.variant = variant & 15;
+  d.prec = (variant >> 4) & 15;  // 0 fp32, 1 bf16, 2 fp32-accurate bf16 split
+  if (d.variant == 9) { d.valu = 1; d.prec = GEMM_F32; d.variant = 0; }  // the fp32 VALU kernel
+  d.diag = (variant >> 12) & 255; // kernel timing diagnostics (results meaningless; 32: A/B switch)
+  // MVAE_BENCH_SPLIT (diagnostics): split-K forced (0 / unset: the planner's)
+  if (const char* sp = std::getenv("MVAE_BENCH_SPLIT"); sp && std::atoi(sp) > 0) d.split = std::atoi(sp);
+  // MVAE_BENCH_TILE_GROUP (diagnostics): the bf16 DMA kernels' tile order (m-tiles per band)
+  if (const char* tg = std::getenv("MVAE_BENCH_TILE_GROUP"); tg && std::atoi(tg) >= 0) d.group = std::atoi(tg);
+  const int np = d.prec == GEMM_F32 ? 0 : (d.prec == GEMM_BF16 ? 1 : 3);
+  float *A = ar.alloc<float>(na), *Bm = ar.alloc<float>(nb), *Cm = ar.alloc<float>(nc);
+  DIAG(ar.err);
+  DIAG(launch_normal(A, 1, 1, (int)na, 1, 0, 1, 0, st));
+  DIAG(launch_normal(Bm, 1, 1, (int)nb, 1, 0, 2, 0, st));
+  d.A = A; d.B = Bm; d.C = Cm;
+  // variant bit 20: A of 0/1 values (the layer-0 pixels; in f32x its residual planes then zero);
+  // bit 21: ... and also as a BitMat per batch (the eight-phase kernel's bits path)
+  const bool bin = (variant >> 20) & 1, use_bits = bin && ((variant >> 21) & 1);
+  if (bin) DIAG(launch_binarize(A, na, st));
+  if (np) {
+    auto* planes = ar.alloc<unsigned short>((size_t)np * (na + nb));
+    DIAG(ar.err);
+    Planes A_{planes, (long long)na, np}, B_{planes + np * na, (long long)nb, np};
+    DIAG(launch_split_planes(A, na, A_, st));
+    DIAG(launch_split_planes(Bm, nb, B_, st));
+    d.Ap = A_.p; d.pA = A_.stride; d.nA = np;
+    d.Bp = B_.p; d.pB = B_.stride; d.nB = np;
+    // a zero flag: the step's pixel operand with its residual planes zero
+    int* bnb = (bin && np == 3) || use_bits ? ar.alloc<int>(4, true) : nullptr;
+    if (bin && np == 3) d.dynA = bnb;
+    if (use_bits) {
+      const int kts = bitmat_kts(K);
+      const size_t bw = bitmat_words(M, K);
+      auto* bits = ar.alloc<unsigned>(bw * batch);
+      DIAG(ar.err);
+      for (int b = 0; b < batch; ++b)
+        DIAG(launch_bits_from_plane(A_.p + (size_t)b * sa, lda, at != 0, M, K, bits + b * bw, kts, bnb + 2, st));
+      d.Abits = bits; d.abits_kts = kts; d.abits_sb = (long long)bw; d.anb = bnb + 2;
+    }
+  }
+  if (const int epi = (variant >> 8) & 15; epi != EPI_STORE)
+    if (int rc = bench_epilogue(ar, d, epi, np, nc)) return rc;
+  const size_t ws_n = gemm_workspace_elems(d);
+  float* ws = ws_n ? ar.alloc<float>(ws_n) : nullptr;
+  hipEvent_t t0 = ar.event(), t1 = ar.event();
+  DIAG(ar.err);
+  for (int i = 0; i < 3; ++i) DIAG(gemm_run(d, ws, ws_n, st));
+  DIAG(hipEventRecord(t0, st));
+  for (int i = 0; i < iters; ++i) DIAG(gemm_run(d, ws, ws_n, st));
+  DIAG(hipEventRecord(t1, st));
+  DIAG(hipEventSynchronize(t1));
+  float ms = 0.f;
+  DIAG(hipEventElapsedTime(&ms, t0, t1));
+  *avg_ms = ms / iters;
+  // MVAE_STAMPS=1 / 2 (diagnostics): one more launch of the stamped ring-kernel / eight-phase
+  // build, summarised on stderr
+  const char* sp = std::getenv("MVAE_STAMPS");
+  std::vector<unsigned long long> h;
+  if (sp && *sp == '1') {
+    const int nmax = 1 << 20;
+    if (int rc = stamped_launch(d, ws, ws_n, st, (size_t)8 * nmax, &h)) return rc;
+    print_ring_stamps(h, nmax, M, N, K);
+  } else if (sp && *sp == '2') {
+    const size_t nmax = 1 << 16;
+    if (int rc = stamped_launch(d, ws, ws_n, st, nmax * 8 * 16, &h)) return rc;
+    print_e8_stamps(h, nmax * 8, M, N, K);
+  }
+  return MVAE_OK;
+}
+
+// One conv2 kernel of the conv tower on caller data (tests only; synchronous): S1 x S1 x 64
+// images, B = batch (3B forward images, 4B backward images). mode 0: out = relu(conv(x, W) + b)
+// over 3B images (y = W2 block [1601][64]); mode 1: out = data gradient conv(x, W rotated) over
+// 4B images (y = W2); mode 2: out[2][1601][64] = the two weight gradients of x = n1 (3B) and
+// y = d a2 (4B). mfma: the bf16 MFMA kernels (operands rounded to bf16) instead of fp32 VALU.
+extern "C" int mvae_debug_conv2(int S1, int B, int mode, int mfma, const float* x, const float* y,
+                                float* out, void* stream) {
+  if (S1 <= 0 || S1 > 50 || B <= 0 || mode < 0 || mode > 2 || !x || !y || !out)
+    return fail(nullptr, MVAE_EINVAL, "mvae_debug_conv2: bad argument");
+  const char* who = "";
+  hipStream_t st = (hipStream_t)stream;
+  Arena ar(st);
+  ConvTower T;
+  T.S1 = S1; T.S = 2 * S1; T.S2 = S1 / 2;
+  // mfma bit 0: the MFMA kernels; the kernel form (the create options' conv2_*): bit 1 the
+  // full-channel forward / data-gradient kernel, bits 2 / 3 its 4 / 16 waves, bit 4 two taps per
+  // slot, bit 5 four M-fragments per wave, bit 6 the 4-wave weight-gradient kernel; bits 8-19 the
+  // weight gradient's chunk count
+  T.mfma = (mfma & 1) != 0;
+  if (mfma & 2) T.conv2_half = false;
+  if (mfma & 4) T.conv2_nw = 4;
+  if (mfma & 8) T.conv2_nw = 16;
+  if (mfma & 16) T.conv2_tpb = 2;
+  if (mfma & 32) T.conv2_fpw = 4;
+  if (mfma & 64) T.conv2_wg8 = false;
+  const size_t img = (size_t)S1 * S1 * 64;
+  const int B2 = 2 * B;
+  T.nchunk2 = std::min(B2, 32);
+  T.nchunk2m = std::min(B2, 64);
+  // bits 8-19: the weight gradient's chunk count (0: the step's defaults above)
+  const int nchunk = (mfma >> 8) & 0xfff;
+  if (nchunk) T.nchunk2 = T.nchunk2m = std::min(B2, nchunk);
+  auto bf16_of = [&](const float* src, size_t n) -> unsigned short* {
+    auto* p = ar.alloc<unsigned short>(n);
+    if (p) ar.err = launch_split_planes(src, n, Planes{p, (long long)n, 1}, st);
+    return p;
+  };
+  if (mode == 2) {
+    T.n1 = const_cast<float*>(x);
+    T.da2 = const_cast<float*>(y);
+    const size_t ns = (size_t)2 * (T.mfma ? T.nchunk2m : T.nchunk2) * (25 * 64 + 1) * 64;
+    T.slab = ar.alloc<float>(ns);
+    DIAG(ar.err);
+    // every chunk writes its whole slab, the empty ones zeros: a slab left unwritten sums to NaN
+    DIAG(hipMemsetAsync(T.slab, 0xff, ns * 4, st));
+    if (T.mfma) { T.n1b = bf16_of(x, 3 * B * img); T.da2b = bf16_of(y, 4 * B * img); }
+    DIAG(ar.err);
+    DIAG(launch_conv2_wgrad(T, B, out, out + (size_t)(25 * 64 + 1) * 64, st));
+  } else {
+    const int nimg = mode == 0 ? 3 * B : 4 * B;
+    const unsigned short* xb = nullptr;
+    if (T.mfma) {
+      xb = bf16_of(x, nimg * img);
+      T.w2f = ar.alloc<unsigned short>(25 * 64 * 64);
+      T.w2d = ar.alloc<unsigned short>(25 * 64 * 64);
+      DIAG(ar.err);
+      DIAG(launch_conv2_wprep(T, y, st));
+    }
+    DIAG(launch_conv2(T, mode == 0, x, xb, y, mode == 0 ? T.w2f : T.w2d, out, nimg, st));
+  }
+  DIAG(hipStreamSynchronize(st));
+  return MVAE_OK;
+}
+
+// One per-pixel kernel of the conv tower on caller buffers (tests only; synchronous): the step's
+// own launcher of conv1_fwd (mode 0), lrn2_pool2_fwd (1), pool2_bwd (2) or conv1_wgrad (3), on a
+// ConvTower whose pointers are the caller's. S: image size; include/mvae.h lists what each mode
+// reads and writes. Only mode 3 allocates (its slab, prefilled with NaN bits).
+extern "C" int mvae_debug_tower(int mode, int S, int n, int ld, int opt, const float* in0, const float* in1,
+                                const float* xs, const unsigned char* arg_in, float* out0, float* out1,
+                                unsigned short* outb, unsigned char* arg_out, void* stream) {
+  const char* who = "mvae_debug_tower: ";
+  auto bad = [&](const std::string& m) { return fail(nullptr, MVAE_EINVAL, who + m); };
+  if (mode < 0 || mode > 3) return bad("mode must be in [0, 3]");
+  if (S < 4 || S > 100 || S % 4) return bad("S must be a multiple of 4 in [4, 100]");
+  if (n < 1 || n > 16384) return bad("n must be in [1, 16384]");
+  ConvTower T;
+  T.S = S; T.S1 = S / 2; T.S2 = S / 4;
+  const bool pixels = mode == 0 || mode == 3;   // ld strides pixel rows, else feature rows
+  if (ld < (pixels ? S * S : T.S2 * T.S2 * 64)) return bad("ld is smaller than a row");
+  hipStream_t st = (hipStream_t)stream;
+  Arena ar(st);
+  if (mode == 0) {
+    if (opt) return bad("opt must be 0 in mode 0");
+    if (!in0 || !in1 || !out0 || !arg_out || (!out1 && !outb)) return bad("null buffer");
+    T.p1 = out0; T.arg1 = arg_out; T.n1 = out1; T.n1b = outb;
+    DIAG(launch_conv1_fwd(T, in0, ld, in1, n, st));
+  } else if (mode == 1) {
+    const int f32 = opt & 1, np = opt >> 1;
+    if (opt < 0 || (np != 0 && np != 1 && np != 3) || (!f32 && !np)) return bad("opt must be f32 | planes << 1, planes 0, 1 or 3");
+    if (!in0 || !arg_out || (f32 && !out0) || (np && !outb)) return bad("null buffer");
+    T.a2 = const_cast<float*>(in0); T.arg2 = arg_out;
+    DIAG(launch_lrn2_pool2_fwd(T, n, out0, ld, f32, Planes{np ? outb : nullptr, (long long)n * ld, np}, st));
+  } else if (mode == 2) {
+    if (opt) return bad("opt must be 0 in mode 2");
+    if (!in0 || !in1 || !arg_in || (!out0 && !outb)) return bad("null buffer");
+    T.a2 = const_cast<float*>(in1); T.arg2 = const_cast<unsigned char*>(arg_in);
+    T.da2 = out0; T.da2b = outb;
+    DIAG(launch_pool2_bwd(T, in0, ld, n, st));
+  } else {
+    if (opt < 0 || opt > (1 << 20)) return bad("opt (the chunk count) must be in [0, 2^20]");
+    if (!in0 || !in1 || !xs || !arg_in || !out0 || !out1) return bad("null buffer");
+    T.dn1 = const_cast<float*>(in0); T.p1 = const_cast<float*>(in1);
+    T.arg1 = const_cast<unsigned char*>(arg_in);
+    T.nchunk1 = std::min(2 * n, opt ? opt : 1024);
+    const size_t ns = (size_t)2 * T.nchunk1 * 26 * 64;
+    T.slab = ar.alloc<float>(ns);
+    DIAG(ar.err);
+    DIAG(hipMemsetAsync(T.slab, 0xff, ns * sizeof(float), st));
+    DIAG(launch_conv1_wgrad(T, xs, ld, n, out0, out1, st));
+  }
+  DIAG(hipStreamSynchronize(st));
+  return MVAE_OK;
+}
+
+// The batch's bit operands on caller buffers (tests only; synchronous; allocates nothing): mode 0
+// launch_make_batch into x then launch_deint_bits (no_xbw: its forward words only), mode 1
+// launch_pairs_bits; mode 2 launch_images_bits (the embedding pass's kernel): `locks` is the one
+// table, idx holds 3B entries (the images of stacked rows 0 .. 3B - 1: three index arrays of B),
+// keys and coef are not read; mode 3 the step's de-interleave alone on the caller's x (the
+// reference of mode 2: x built by the host). S x S images, B rows. Caller buffers, zero-filled (padding is never written):
+// xbf bitmat_words(3B, D + 1) words, xbw bitmat_words(D + 1, 3B) words, xbits [B][ldbits] bytes,
+// dyn 4 ints, plane [3B][ldx] bf16 (plane 0, written when the not-binary word rises), x [B][3D]
+// floats (mode 0 only).
+static int debug_bits(const char* caller, const unsigned char* locks, const unsigned char* keys, const int* idx,
+                      const int* kidx, const float* coef, int B, int S, float divisor, int mode, int no_xbw,
+                      float* x, unsigned* xbf, unsigned* xbw, unsigned char* xbits, int ldbits, int* dyn,
+                      unsigned short* plane, int ldx, void* stream) {
+  const std::string w(caller);
+  const char* who = "";
+  const bool pairs_mode = mode == 0 || mode == 1;
+  if ((mode != 3 && (!locks || !idx)) || (pairs_mode && (!keys || !coef)) || B <= 0 || S <= 0 || S > 4096 ||
+      !(divisor > 0.f) || mode < 0 || mode > 3 || ((mode == 0 || mode == 3) && !x) || !xbf || !xbw || !xbits || !dyn || !plane || ldx < S * S || ldbits < (S * S + 7) / 8)
+    return fail(nullptr, MVAE_EINVAL, w + ": bad argument");
+  hipStream_t st = (hipStream_t)stream;
+  const int D = S * S;
+  const Planes pl{plane, (long long)3 * B * ldx, 1};
+  const int kts_f = bitmat_kts(D + 1), kts_w = bitmat_kts(3 * B);
+  hipError_t e;
+  if (mode == 0 || mode == 3) {  // x from the tables / the caller's x, then the step's de-interleave
+    const bool served = !((D % 8) || (B % 64) || (ldx % 8));
+    e = mode == 0 ? launch_make_batch(locks, keys, S, S, idx, kidx, coef, B, divisor, x, st)
+                  : (served ? hipSuccess : hipErrorInvalidValue);
+    if (e == hipSuccess)
+      e = launch_deint_bits(x, B, D, xbf, kts_f, xbw, kts_w, xbits, ldbits, dyn, dyn + 1, nullptr, pl, ldx, 0,
+                            no_xbw != 0, st);
+  } else if (mode == 1) {
+    e = launch_pairs_bits(locks, keys, S, S, idx, kidx, coef, divisor, B, xbf, kts_f, xbw, kts_w, xbits, ldbits, dyn,
+                          dyn + 1, nullptr, pl, ldx, 0, no_xbw != 0, st);
+  } else {
+    e = launch_images_bits(locks, S, S, idx, 3 * B, divisor, B, xbf, kts_f, xbw, kts_w, xbits, ldbits, dyn, dyn + 1,
+                           nullptr, pl, ldx, 0, no_xbw != 0, st);
+  }
+  if (e == hipErrorInvalidValue)
+    return fail(nullptr, MVAE_EINVAL, w + ": shape or alignment the kernels do not serve");
+  DIAG(e);
+  DIAG(hipStreamSynchronize(st));
+  return MVAE_OK;
+}
+
+extern "C" int mvae_debug_pairs_bits(const unsigned char* locks, const unsigned char* keys, const int* idx,
+                                     const float* coef, int B, int S, float divisor, int mode, int no_xbw,
+                                     float* x, unsigned* xbf, unsigned* xbw, unsigned char* xbits, int ldbits,
+                                     int* dyn, unsigned short* plane, int ldx, void* stream) {
+  return debug_bits("mvae_debug_pairs_bits", locks, keys, idx, nullptr, coef, B, S, divisor, mode, no_xbw, x, xbf,
+                    xbw, xbits, ldbits, dyn, plane, ldx, stream);
+}
+
+// modes 0 and 1 with the key of each row from key_idx (NULL: idx)
+extern "C" int mvae_debug_xpairs_bits(const unsigned char* locks, const unsigned char* keys, const int* idx,
+                                      const int* key_idx, const float* coef, int B, int S, float divisor, int mode,
+                                      int no_xbw, float* x, unsigned* xbf, unsigned* xbw, unsigned char* xbits,
+                                      int ldbits, int* dyn, unsigned short* plane, int ldx, void* stream) {
+  if (mode != 0 && mode != 1) return fail(nullptr, MVAE_EINVAL, "mvae_debug_xpairs_bits: mode must be 0 or 1");
+  return debug_bits("mvae_debug_xpairs_bits", locks, keys, idx, key_idx, coef, B, S, divisor, mode, no_xbw, x, xbf,
+                    xbw, xbits, ldbits, dyn, plane, ldx, stream);
+}
+
+// The fused hidden-layer chain on caller buffers (tests only; synchronous; allocates nothing): fills a
+// ChainArgs as mvae_plan.cpp's chain_of does and launches the step's kernel. Everything the kernel's
+// addressing relies on is checked here, before any HIP call: it reads 16-B chunks of x up to
+// min(ldx, 512) columns, of W_l up to round8(N_l) columns of its K_l rows, and writes
+// round8(N_l + 1) columns of out_l's first M rows.
+extern "C" int mvae_debug_chain(int M, int nl, const int* K, const int* N, int act, int rows,
+                                const unsigned short* x, int ldx, const unsigned short* const* w,
+                                const int* ldw, unsigned short* const* out, const int* ldo, void* stream) {
+  const char* who = "mvae_debug_chain: ";
+  auto bad = [&](const std::string& m) { return fail(nullptr, MVAE_EINVAL, who + m); };
+  if (nl < 1 || nl > 4) return bad("nl must be in [1, 4]");
+  if (M < 1) return bad("M must be at least 1");
+  if (act != 0 && act != 1) return bad("act must be 0 (tanh) or 1 (elu)");
+  if (rows != 0 && (rows < 16 || rows > 96 || rows % 16))
+    return bad("rows must be 0 or a multiple of 16 in [16, 96]");
+  if (!K || !N || !w || !ldw || !out || !ldo) return bad("null K, N, w, ldw, out or ldo array");
+  if (!x || misaligned(x)) return bad("x is null or not 16-byte aligned");
+  if (ldx < 8 || (ldx & 7)) return bad("ldx must be a positive multiple of 8");
+  ChainArgs ca;
+  ca.x = x; ca.ldx = ldx; ca.M = M; ca.nl = nl; ca.act = act; ca.rows = rows;
+  for (int l = 0; l < nl; ++l) {
+    const std::string at = " (layer " + std::to_string(l) + ")";
+    if (K[l] < 1 || K[l] > 512) return bad("K must be in [1, 512]" + at);
+    if (N[l] < 1 || N[l] > 511) return bad("N must be in [1, 511]" + at);
+    if (l == 0 && K[0] > ldx) return bad("K[0] exceeds ldx");
+    if ((ldw[l] & 7) || ldw[l] < ((N[l] + 7) & ~7))
+      return bad("ldw must be a multiple of 8, at least round8(N)" + at);
+    if ((ldo[l] & 7) || ldo[l] < ((N[l] + 8) & ~7))
+      return bad("ldo must be a multiple of 8, at least round8(N + 1)" + at);
+    if (!w[l] || misaligned(w[l])) return bad("w is null or not 16-byte aligned" + at);
+    if (!out[l] || misaligned(out[l])) return bad("out is null or not 16-byte aligned" + at);
+    ChainLayer& cl = ca.l[l];
+    cl.w = w[l]; cl.ldw = ldw[l]; cl.K = K[l]; cl.N = N[l]; cl.out = out[l]; cl.ldo = ldo[l];
+  }
+  hipStream_t st = (hipStream_t)stream;
+  DIAG(launch_enc_chain(ca, st));
+  DIAG(hipStreamSynchronize(st));
+  return MVAE_OK;
+}
+
+// One kernel of the latent head on caller buffers (tests only; synchronous; allocates nothing): the
+// step's own launcher of latent_fwd, colstats, metric, loss_reduce or latent_bwd, with the plane
+// strides the step uses (the whole fp32 buffer: 3B ldz resp. 4B ldh elements). Everything the
+// kernels' addressing relies on is checked here, before any HIP call; include/mvae.h lists what
+// each mode reads and writes.
+extern "C" int mvae_debug_head(const mvae_head_args* args, void* stream) {
+  const char* who = "mvae_debug_head: ";
+  auto bad = [&](const std::string& m) { return fail(nullptr, MVAE_EINVAL, who + m); };
+  if (!args) return bad("args is NULL");
+  const mvae_head_args& a = *args;
+  if (a.mode < MVAE_HEAD_FWD || a.mode > MVAE_HEAD_BWD) return bad("mode must be in [0, 4]");
+  if (a.B < 1 || a.L < 1) return bad("B and L must be at least 1");
+  if (a.B > (1 << 24) || a.L > (1 << 20)) return bad("B or L too large");
+  if (a.Bg < a.B) return bad("Bg must be at least B");
+  const int B = a.B, L = a.L;
+  const float inv_bg = 1.f / (float)a.Bg;
+  const bool uses_z = a.mode == MVAE_HEAD_FWD || a.mode == MVAE_HEAD_COLSTATS || a.mode == MVAE_HEAD_METRIC;
+  if (uses_z && a.ldz < L) return bad("ldz is smaller than a row");
+  if (a.mode == MVAE_HEAD_BWD && a.ldh < 2 * L) return bad("ldh is smaller than a row");
+  LatentEps le;
+  if (a.mode == MVAE_HEAD_FWD || a.mode == MVAE_HEAD_BWD) {
+    if (!a.ms) return bad("ms is NULL");
+    le.buf = a.eps; le.seed = a.seed; le.counter = a.counter; le.Bg = a.Bg; le.off = a.off;
+    if (!a.eps && (a.off < 0 || a.off > a.Bg - B)) return bad("off outside [0, Bg - B]");
+  }
+  hipStream_t st = (hipStream_t)stream;
+  if (a.mode == MVAE_HEAD_FWD) {
+    const int np = a.z_planes;
+    if (a.zmask & ~6) return bad("zmask must be 0, 2, 4 or 6");
+    if (np != 0 && np != 1 && np != 3) return bad("z_planes must be 0, 1 or 3");
+    if (!a.rowfwd || (a.zmask && !a.z) || (np && !a.zp)) return bad("null buffer");
+    if (misaligned(a.rowfwd)) return bad("rowfwd is not 16-byte aligned");
+    if (L % 4 == 0 && a.ldz % 4 == 0 &&
+        (misaligned(a.ms) || misaligned(a.eps) || (a.zmask && misaligned(a.z)) || (np && misaligned(a.zp))))
+      return bad("ms, eps, z or zp is not 16-byte aligned");
+    DIAG(launch_latent_fwd(a.ms, le, a.z, Planes{np ? a.zp : nullptr, (long long)3 * B * a.ldz, np}, a.zmask, B, L,
+                           a.ldz, a.rowfwd, st));
+  } else if (a.mode == MVAE_HEAD_COLSTATS) {
+    if (a.cs_mode != 0 && a.cs_mode != 1) return bad("cs_mode must be 0 or 1");
+    if (!a.z || !a.part || !a.out || (a.cs_mode == 1 && (!a.colsq || !a.draw))) return bad("null buffer");
+    DIAG(launch_colstats(a.cs_mode, a.z, B, L, a.ldz, a.colsq, a.draw, a.part, colstats_nchunk(B), a.out, st, a.cnt));
+  } else if (a.mode == MVAE_HEAD_METRIC) {
+    if (a.metric != 0 && a.metric != 1) return bad("metric must be 0 (cosine) or 1 (sqdiff)");
+    if (a.nblk < 0) return bad("nblk must not be negative");
+    if (!a.z || !a.rowfwd || (a.nblk && !a.rowpart) || (a.metric == 0 && !a.colsq) || !a.rowvals || !a.dist ||
+        !a.draw)
+      return bad("null buffer");
+    if (misaligned(a.rowfwd)) return bad("rowfwd is not 16-byte aligned");
+    if (a.metric == 0 && L % 4 == 0 && L >= 64 && a.ldz % 4 == 0 && misaligned(a.z))
+      return bad("z is not 16-byte aligned");
+    DIAG(launch_metric(a.z, a.ldz, a.rowfwd, a.rowpart, a.nblk, a.areas, a.colsq, B, L, a.metric, a.recip != 0, a.w,
+                       inv_bg, a.rowvals, a.dist, a.draw, st));
+  } else if (a.mode == MVAE_HEAD_LOSS) {
+    if (!a.rowvals || !a.losses) return bad("null buffer");
+    if (misaligned(a.rowvals)) return bad("rowvals is not 16-byte aligned");
+    DIAG(launch_loss_reduce(a.rowvals, B, inv_bg, a.losses, st));
+  } else {
+    const int np = a.h_planes;
+    if (a.metric != 0 && a.metric != 1) return bad("metric must be 0 (cosine) or 1 (sqdiff)");
+    if (np != 0 && np != 1 && np != 3) return bad("h_planes must be 0, 1 or 3");
+    if (!a.dhead && !np) return bad("neither dhead nor planes to write");
+    if (!a.dzdec || !a.draw || (a.metric == 0 && (!a.colsq || !a.coldot)) || (np && !a.hp)) return bad("null buffer");
+    if (L % 4 == 0 && a.ldh % 4 == 0 &&
+        (misaligned(a.ms) || misaligned(a.eps) || misaligned(a.dzdec) || misaligned(a.dhead) || (np && misaligned(a.hp))))
+      return bad("ms, eps, dzdec, dhead or hp is not 16-byte aligned");
+    DIAG(launch_latent_bwd(a.ms, le, a.dzdec, a.draw, a.colsq, a.coldot, B, L, a.metric, a.w, inv_bg, a.dhead, a.ldh,
+                           Planes{np ? a.hp : nullptr, (long long)4 * B * a.ldh, np}, st));
+  }
+  DIAG(hipStreamSynchronize(st));
+  return MVAE_OK;
+}

@@ -123,3 +123,14 @@ def test_build_id_ignores_stray_files_and_names_missing_sources(tmp_path, monkey
     monkeypatch.setattr(build, "SOURCES", build.SOURCES + ["does_not_exist.hip"])
     with pytest.raises(_lib.MVAELibraryError, match="does_not_exist.hip"):
         _lib.verify_build(lib)
+
+
+def test_every_native_source_is_in_the_build():
+    """Every *.cpp, *.hip and *.h under csrc/ is named in SOURCES or HEADERS, so a new file cannot
+    be compiled from, or included, while staying outside the build id."""
+    from magic_amd import build
+    named = {os.path.normpath(os.path.join(build.CSRC, f)) for f in build.SOURCES + build.HEADERS}
+    on_disk = {os.path.join(build.CSRC, f) for f in os.listdir(build.CSRC)
+               if f.endswith((".cpp", ".hip", ".h"))}
+    assert on_disk and not sorted(on_disk - named)
+    assert all(os.path.isfile(p) for p in named)

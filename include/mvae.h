@@ -595,6 +595,59 @@ typedef struct mvae_head_args {
   unsigned short* hp;
 } mvae_head_args;
 int mvae_debug_head(const mvae_head_args* args, void* stream);
+/* One GEMM with a fused epilogue of the step on caller data, through gemm_run (tests; synchronous;
+ * allocates the operands' bf16 planes and a split-K workspace, nothing the epilogue touches). Every
+ * pointer is a device pointer; a zeroed field is a NULL / 0 argument. v = A B with A [M][lda] and
+ * B [K][ldb], or [N][ldb] with bt, in fp32; prec 0 fp32, 1 bf16, 2 f32x (the operands' planes are
+ * split here); variant as mvae_debug_gemm's (0 the planner's, 3, 4, 10, 11, 12, 13); x3: the
+ * plane-stacked kernel where it serves. The output goes to du [M][ldc] fp32 (or NULL) and to ncp
+ * (0, 1 or 3) bf16 planes cp [ncp][pc], same ld.
+ *  MVAE_EPI_ACT: out = act(v). MVAE_EPI_DACT: out = v act'(aux[r']) with aux [.][ld_aux] fp32, or its
+ *    bf16 image auxp (same ld) when set; r' = r < remap_split ? r : r - remap_shift (zeroed: r' = r),
+ *    so aux holds max(min(M, remap_split), M - remap_shift) rows. padw 1 / 2 (both modes): the
+ *    padding columns [N, round8(N)) may be read (aux) and written as whole 8-column chunks, 1.0 at
+ *    column N with padw 2, else 0: every ld then a multiple of 8, at least round8(N).
+ *  MVAE_EPI_BCE: y = sigmoid(v); rowpart[r][rp_off + b] = -sum over the columns of 128-column block
+ *    b of x log y + (1 - x) log(1 - y) (each product 0 where its factor is 0; no epsilon), rowpart
+ *    [M][rp_ld] (rp_ld 0: ceil(N / 128), rp_off then 0); out = (y - x) scale; y [M][ldy] or NULL.
+ *    The target: x [M][ldx] fp32, always given; in the plane modes also xp, its bf16 plane (same
+ *    ld), read instead while dyn[0] == 0, and xbits [M][ldbits] (byte c of a row = columns 8c .. 8c
+ *    + 7, bit j = column 8c + j nonzero), read instead while dyn[2] == 0; dyn: 4 ints, the
+ *    de-interleave's flag words (mvae_debug_pairs_bits). split_c0 > 0 (plane modes): two launches
+ *    as the step's split head makes them, columns [0, c0) on the requested variant and [c0, N) on
+ *    the ring kernel at tile N 128.
+ * MVAE_EINVAL with a message, before any HIP call: args NULL, another mode / act / prec / variant /
+ * x3, a size < 1, a stride smaller than its row, ncp not 0, 1 or 3, neither du nor planes, pc <
+ * M ldc, a bad remap or padw, BCE with rowpart NULL, rp_ld < rp_off + ceil(N / 128) (rp_ld 0: rp_off
+ * != 0), split_c0 not a multiple of 256, leaving fewer than 128 columns or in fp32 precision, xp or
+ * xbits without dyn, xbits without xp, ldbits < ceil(N / 8), a NULL among the buffers a mode names. */
+enum { MVAE_EPI_ACT = 1, MVAE_EPI_DACT = 2, MVAE_EPI_BCE = 3 };
+typedef struct mvae_epi_args {
+  int M, N, K;
+  int lda, ldb, bt;
+  int prec, variant, x3;
+  int epi, act;
+  int ldc, ncp;
+  int ldx, ldbits, ldy;             /* BCE */
+  int rp_ld, rp_off, split_c0;
+  int ld_aux, remap_split, remap_shift; /* DACT */
+  int padw;                         /* ACT / DACT */
+  float scale;                      /* BCE */
+  long long pc;                     /* plane stride of cp, elements */
+  const float* A;
+  const float* B;
+  float* du;
+  unsigned short* cp;
+  const float* x;
+  const unsigned short* xp;
+  const int* dyn;
+  const unsigned char* xbits;
+  float* y;
+  float* rowpart;
+  const float* aux;
+  const unsigned short* auxp;
+} mvae_epi_args;
+int mvae_debug_epi(const mvae_epi_args* args, void* stream);
 
 #ifdef __cplusplus
 }

@@ -87,6 +87,23 @@ class mvae_head_args(C.Structure):
                 ("losses", C.c_void_p), ("dhead", C.c_void_p), ("hp", C.c_void_p)]
 
 
+EPI_ACT, EPI_DACT, EPI_BCE = 1, 2, 3
+
+
+class mvae_epi_args(C.Structure):
+    """Arguments of ``mvae_debug_epi`` (``include/mvae.h``): sizes and device pointers; a zeroed
+    field is a NULL / 0 argument."""
+    _fields_ = [("M", C.c_int), ("N", C.c_int), ("K", C.c_int), ("lda", C.c_int), ("ldb", C.c_int),
+                ("bt", C.c_int), ("prec", C.c_int), ("variant", C.c_int), ("x3", C.c_int), ("epi", C.c_int),
+                ("act", C.c_int), ("ldc", C.c_int), ("ncp", C.c_int), ("ldx", C.c_int), ("ldbits", C.c_int),
+                ("ldy", C.c_int), ("rp_ld", C.c_int), ("rp_off", C.c_int), ("split_c0", C.c_int),
+                ("ld_aux", C.c_int), ("remap_split", C.c_int), ("remap_shift", C.c_int), ("padw", C.c_int),
+                ("scale", C.c_float), ("pc", C.c_longlong),
+                ("A", C.c_void_p), ("B", C.c_void_p), ("du", C.c_void_p), ("cp", C.c_void_p),
+                ("x", C.c_void_p), ("xp", C.c_void_p), ("dyn", C.c_void_p), ("xbits", C.c_void_p),
+                ("y", C.c_void_p), ("rowpart", C.c_void_p), ("aux", C.c_void_p), ("auxp", C.c_void_p)]
+
+
 class mvae_tensor(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("data", C.c_void_p), ("rows", C.c_int),
                 ("cols", C.c_int), ("ld", C.c_int), ("trained_by", C.c_int)]
@@ -186,6 +203,7 @@ _SIGS = {
                           C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int),
                           C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_void_p], C.c_int),
     "mvae_debug_head": ([C.POINTER(mvae_head_args), C.c_void_p], C.c_int),
+    "mvae_debug_epi": ([C.POINTER(mvae_epi_args), C.c_void_p], C.c_int),
 }
 
 EXPORTED = tuple(_SIGS)

@@ -213,6 +213,9 @@ std::string& create_err();  // this thread's error of a call without a context (
 int validate(const mvae_cfg* cfg);
 int parse_opts(const char* s, CreateOpts* o);
 int plan_context(mvae_ctx* ctx, const CreateOpts& opt);
+// the BCE head f as two launches: *a its columns [0, c0), *b the columns [c0, N) on the ring kernel
+// at tile N 128 (c0 a multiple of 256; plan_bce_split and mvae_debug_epi)
+void bce_split_descs(const GemmDesc& f, int c0, GemmDesc* a, GemmDesc* b);
 }  // namespace mvae
 
 static inline int fail(mvae_ctx* ctx, int code, const std::string& msg) {

@@ -686,3 +686,109 @@ extern "C" int mvae_debug_head(const mvae_head_args* args, void* stream) {
   DIAG(hipStreamSynchronize(st));
   return MVAE_OK;
 }
+
+// One GEMM with a fused epilogue of the step on caller buffers (tests only; synchronous): builds the
+// GemmDesc the step's wiring would and calls gemm_run, as mvae_debug_gemm does, with every GemmEpi
+// field the step sets -- the BCE head (all target and output forms, rowpart's stride and first
+// block, the two launches of plan_bce_split through bce_split_descs), the dgrad's row remap and bf16
+// aux, the padded rows' whole-chunk stores. Allocates the operands' planes and a split-K workspace;
+// everything the epilogue reads or writes is the caller's. Everything the kernels' addressing relies
+// on is checked here, before any HIP call; include/mvae.h lists the fields.
+extern "C" int mvae_debug_epi(const mvae_epi_args* args, void* stream) {
+  const char* who = "mvae_debug_epi: ";
+  auto bad = [&](const std::string& m) { return fail(nullptr, MVAE_EINVAL, who + m); };
+  if (!args) return bad("args is NULL");
+  const mvae_epi_args& a = *args;
+  if (a.epi != MVAE_EPI_ACT && a.epi != MVAE_EPI_DACT && a.epi != MVAE_EPI_BCE) return bad("epi must be 1 (ACT), 2 (DACT) or 3 (BCE)");
+  if (a.M < 1 || a.N < 1 || a.K < 1) return bad("M, N and K must be at least 1");
+  if (a.M > (1 << 24) || a.N > (1 << 24) || a.K > (1 << 24)) return bad("M, N or K too large");
+  if (a.prec < GEMM_F32 || a.prec > GEMM_F32X) return bad("prec must be 0, 1 or 2");
+  {
+    const int v = a.variant;
+    if (v != 0 && v != 3 && v != 4 && !(v >= 10 && v <= 13)) return bad("variant must be 0, 3, 4, 10, 11, 12 or 13");
+  }
+  if (a.x3 < 0 || a.x3 > 2) return bad("x3 must be in [0, 2]");
+  if (a.act != ACT_TANH && a.act != ACT_ELU) return bad("act must be 0 (tanh) or 1 (elu)");
+  if (a.bt != 0 && a.bt != 1) return bad("bt must be 0 or 1");
+  if (!a.A || !a.B) return bad("A or B is NULL");
+  if (a.lda < a.K) return bad("lda is smaller than a row");
+  if (a.ldb < (a.bt ? a.K : a.N)) return bad("ldb is smaller than a row");
+  if (a.ncp != 0 && a.ncp != 1 && a.ncp != 3) return bad("ncp must be 0, 1 or 3");
+  if (!a.du && !a.ncp) return bad("neither du nor planes to write");
+  if (a.ncp && !a.cp) return bad("cp is NULL");
+  if (a.ldc < a.N) return bad("ldc is smaller than a row");
+  if (a.ncp && a.pc < (long long)a.M * a.ldc) return bad("pc is smaller than a plane");
+  const int n8 = (a.N + 7) & ~7, nblk = gemm_bce_nblk(a.N);
+  const bool bce = a.epi == MVAE_EPI_BCE;
+  if (a.padw < 0 || a.padw > 2 || (bce && a.padw)) return bad("padw must be 0, 1 or 2 (0 with BCE)");
+  if (a.padw && ((a.ldc & 7) || a.ldc < n8)) return bad("padw: ldc must be a multiple of 8, at least round8(N)");
+  if (a.split_c0 && !bce) return bad("split_c0 is the BCE head's");
+  if (a.epi == MVAE_EPI_DACT) {
+    if (!a.aux && !a.auxp) return bad("aux and auxp are NULL");
+    if (a.ld_aux < a.N) return bad("ld_aux is smaller than a row");
+    if (a.padw && ((a.ld_aux & 7) || a.ld_aux < n8)) return bad("padw: ld_aux must be a multiple of 8, at least round8(N)");
+    if (a.remap_split < 0 || a.remap_shift < 0 || a.remap_shift > a.remap_split)
+      return bad("remap must satisfy 0 <= remap_shift <= remap_split");
+  }
+  if (bce) {
+    if (!a.x) return bad("x is NULL");
+    if (a.ldx < a.N) return bad("ldx is smaller than a row");
+    if (!a.rowpart) return bad("rowpart is NULL");
+    if (a.rp_off < 0 || (a.rp_ld ? a.rp_ld < a.rp_off + nblk : a.rp_off != 0))
+      return bad("rp_ld is smaller than rp_off plus the launch's blocks");
+    if (a.y && a.ldy < a.N) return bad("ldy is smaller than a row");
+    if ((a.xp || a.xbits) && !a.dyn) return bad("xp or xbits without dyn");
+    if (a.xbits && !a.xp) return bad("xbits without xp");
+    if (a.xbits && a.ldbits < (a.N + 7) / 8) return bad("ldbits is smaller than a row");
+    if (a.split_c0 < 0 || a.split_c0 % 256 || (a.split_c0 && a.N - a.split_c0 < 128))
+      return bad("split_c0 must be a multiple of 256 that leaves at least 128 columns");
+    if (a.split_c0 && (a.prec == GEMM_F32 || a.bt || a.M < 128))
+      return bad("split_c0 needs a plane mode, bt = 0 and M >= 128");
+  }
+  hipStream_t st = (hipStream_t)stream;
+  Arena ar(st);
+  GemmDesc d = gd(a.M, a.N, a.K, a.A, a.lda, false, a.B, a.ldb, a.bt != 0, a.du, a.ldc, a.epi);
+  d.prec = a.prec;
+  d.variant = a.variant;
+  d.x3 = a.x3;
+  GemmEpi& e = d.epi;
+  e.act = a.act;
+  e.c32 = a.du ? 1 : 0;
+  if (a.ncp) { e.cp = a.cp; e.pc = a.pc; e.ncp = a.ncp; }
+  e.padw = a.padw;
+  if (a.epi == MVAE_EPI_DACT) {
+    e.aux = a.aux; e.auxp = a.auxp; e.ld_aux = a.ld_aux;
+    e.remap_split = a.remap_split; e.remap_shift = a.remap_shift;
+  }
+  if (bce) {
+    e.x = a.x; e.ldx = a.ldx; e.scale = a.scale;
+    if (a.xp) { e.xp = a.xp; e.xdyn = a.dyn; e.xnb = a.dyn + 2; }  // the step's layout of the flag words
+    if (a.xbits) { e.xbits = a.xbits; e.ldbits = a.ldbits; }
+    e.y = a.y; e.ldy = a.ldy;
+    e.rowpart = a.rowpart; e.rp_ld = a.rp_ld; e.rp_off = a.rp_off;
+  }
+  if (d.prec != GEMM_F32) {  // plane images of the operands (the step's producers write these)
+    const int np = d.prec == GEMM_BF16 ? 1 : 3;
+    const size_t na = (size_t)a.M * a.lda, nb = (size_t)(a.bt ? a.N : a.K) * a.ldb;
+    Planes A_{ar.alloc<unsigned short>(np * na), (long long)na, np};
+    Planes B_{ar.alloc<unsigned short>(np * nb), (long long)nb, np};
+    DIAG(ar.err);
+    DIAG(launch_split_planes(a.A, na, A_, st));
+    DIAG(launch_split_planes(a.B, nb, B_, st));
+    d.Ap = A_.p; d.pA = A_.stride; d.nA = np;
+    d.Bp = B_.p; d.pB = B_.stride; d.nB = np;
+  }
+  if (a.split_c0) {  // a BCE-epilogue GEMM never splits K: no workspace
+    GemmDesc da, db;
+    bce_split_descs(d, a.split_c0, &da, &db);
+    DIAG(gemm_run(da, nullptr, 0, st));
+    DIAG(gemm_run(db, nullptr, 0, st));
+  } else {
+    const size_t ws_n = gemm_workspace_elems(d);
+    float* ws = ws_n ? ar.alloc<float>(ws_n) : nullptr;
+    DIAG(ar.err);
+    DIAG(gemm_run(d, ws, ws_n, st));
+  }
+  DIAG(hipStreamSynchronize(st));
+  return MVAE_OK;
+}

@@ -589,23 +589,7 @@ int plan_bce_split(mvae_ctx* c, const CreateOpts& opt) {
   if (!(opt.bce_split && plane_kernel(f) && tiles > 256 && tiles % 256 != 0 && tiles % 256 <= 128 && n1 >= 1 &&
         n1 < tn && f.N - 256 * n1 >= 128))
     return MVAE_OK;
-  const int c0 = (int)(256 * n1);
-  GemmDesc a = f, b = f;
-  a.N = c0;
-  a.epi.rp_ld = gemm_bce_nblk(f.N);
-  b.N = f.N - c0;
-  b.B = f.B + c0;
-  if (b.Bp) b.Bp = f.Bp + c0;
-  if (b.C) b.C = f.C + c0;
-  if (b.epi.cp) b.epi.cp = f.epi.cp + c0;
-  if (b.epi.x) b.epi.x = f.epi.x + c0;
-  if (b.epi.xp) b.epi.xp = f.epi.xp + c0;
-  if (b.epi.xbits) b.epi.xbits = f.epi.xbits + c0 / 8;  // (c0: a multiple of 256)
-  b.epi.rp_ld = gemm_bce_nblk(f.N);
-  b.epi.rp_off = c0 / 128;
-  b.variant = 11;  // the ring kernel at 256x128 tiles
-  c->f_out_a = a;
-  c->f_out_b = b;
+  bce_split_descs(f, (int)(256 * n1), &c->f_out_a, &c->f_out_b);
   c->f_split = true;
   return MVAE_OK;
 }
@@ -715,6 +699,28 @@ int make_streams(mvae_ctx* c, const CreateOpts&) {
 }
 
 }  // namespace
+
+// (B [K][ldb]: the head is never bt; rowpart keeps f's row stride and first block when it sets them)
+void mvae::bce_split_descs(const GemmDesc& f, int c0, GemmDesc* pa, GemmDesc* pb) {
+  GemmDesc a = f, b = f;
+  const int rp_ld = f.epi.rp_ld ? f.epi.rp_ld : gemm_bce_nblk(f.N);
+  a.N = c0;
+  a.epi.rp_ld = rp_ld;
+  b.N = f.N - c0;
+  b.B = f.B + c0;
+  if (b.Bp) b.Bp = f.Bp + c0;
+  if (b.C) b.C = f.C + c0;
+  if (b.epi.cp) b.epi.cp = f.epi.cp + c0;
+  if (b.epi.x) b.epi.x = f.epi.x + c0;
+  if (b.epi.xp) b.epi.xp = f.epi.xp + c0;
+  if (b.epi.xbits) b.epi.xbits = f.epi.xbits + c0 / 8;  // (c0: a multiple of 256)
+  if (b.epi.y) b.epi.y = f.epi.y + c0;
+  b.epi.rp_ld = rp_ld;
+  b.epi.rp_off = f.epi.rp_off + c0 / 128;
+  b.variant = 11;  // the ring kernel at 256x128 tiles
+  *pa = a;
+  *pb = b;
+}
 
 int mvae::plan_context(mvae_ctx* c, const CreateOpts& opt) {
   hipError_t he = hipSetDevice(c->device);

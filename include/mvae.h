@@ -463,8 +463,8 @@ int mvae_timing_reset(mvae_ctx* ctx);
 /* One GEMM of the step's kernel family: C[M,N] = epi(A[M,K] B[K,N]); A stored [M][K]
  * (at=0) or [K][M] (at=1), B stored [K][N] (bt=0) or [N][K] (bt=1). epi: 0 store,
  * 1 act (act: 0 tanh, 1 elu), 2 C = acc * act'(aux), 4 sigmoid; epi | (prec << 4) |
- * (variant << 8) selects the arithmetic (MVAE_PREC_*) and kernel (0 auto, 3 the 256x256
- * bf16 kernel, 4 the 128x128 one, 9 the fp32 VALU kernel for skinny shapes). Workspace is allocated and freed inside
+ * (variant << 8) selects the arithmetic (MVAE_PREC_*) and the kernel (the table of kernel numbers
+ * at mvae_debug_plan below; 0 the planner's choice). Workspace is allocated and freed inside
  * (synchronous; tests only). mvae_bench_gemm: variant | (prec << 4) | (epi << 8).    */
 int mvae_bench_gemm(int M, int N, int K, int at, int bt, int batch, int variant, int iters,
                     void* stream, float* avg_ms);
@@ -599,7 +599,7 @@ int mvae_debug_head(const mvae_head_args* args, void* stream);
  * allocates the operands' bf16 planes and a split-K workspace, nothing the epilogue touches). Every
  * pointer is a device pointer; a zeroed field is a NULL / 0 argument. v = A B with A [M][lda] and
  * B [K][ldb], or [N][ldb] with bt, in fp32; prec 0 fp32, 1 bf16, 2 f32x (the operands' planes are
- * split here); variant as mvae_debug_gemm's (0 the planner's, 3, 4, 10, 11, 12, 13); x3: the
+ * split here); variant: a kernel number (mvae_debug_plan's table: 0, 3, 4, 10, 11, 12 or 13); x3: the
  * plane-stacked kernel where it serves. The output goes to du [M][ldc] fp32 (or NULL) and to ncp
  * (0, 1 or 3) bf16 planes cp [ncp][pc], same ld.
  *  MVAE_EPI_ACT: out = act(v). MVAE_EPI_DACT: out = v act'(aux[r']) with aux [.][ld_aux] fp32, or its
@@ -648,6 +648,72 @@ typedef struct mvae_epi_args {
   const unsigned short* auxp;
 } mvae_epi_args;
 int mvae_debug_epi(const mvae_epi_args* args, void* stream);
+/* Which kernel a GEMM would run on, and how: the plan gemm_run would launch for these arguments,
+ * computed on the host alone (no HIP call, no GPU needed; a pointer is never followed, only its
+ * low four bits are read). Tests pin the planner with it (tests/test_gemm_plan.py).
+ * In: the shape, layouts and strides (elements); prec as mvae_debug_gemm's, nA / nB operand planes,
+ * dynA != 0: A's residual planes flagged at run time; epi 0 store, 1 act, 2 dact, 3 BCE, 4 sigmoid
+ * with the GemmEpi fields the choice reads (cp / auxp / xp non-NULL: set; c32, xdyn, padw); abits:
+ * A also given as bits; x3 as mvae_debug_epi's; tm 0 / 192 / 256 and split > 0 forced; valu != 0
+ * the fp32 VALU kernel forced; variant: the table below; max_ws: the workspace in floats (0: none),
+ * at ws.
+ * Out: kernel (MVAE_KERNEL_*), staging (the 128x128 kernels' diagnostic forms 1 / 2), the tile tm x
+ * tn, the grid's ntm x ntn tiles and tile order group, split and kchunk (k per slice), lds_epilogue
+ * (the row-major epilogue through LDS, else the accumulator layout's), vec_epilogue (its 16-byte
+ * accesses), epi_launched (the kernel instantiation: 0-4, 5 BCE choosing its target form at run
+ * time, 6 dact reading the bf16 aux), ws_elems (floats of split-K slabs), valu_fits (the step's
+ * wiring would move this GEMM to the VALU kernel), refused (gemm_run returns an error: the slabs
+ * exceed max_ws).
+ * MVAE_EINVAL with a message: NULL arguments, sizes < 1, prec / epi / variant / tm / x3 out of range.
+ *
+ * The kernel numbers ("variant") of mvae_debug_gemm, mvae_bench_gemm, mvae_debug_epi and this call;
+ * 9 is not in mvae_debug_epi; a number above 15 does not exist. Inside the library they are named forces:
+ *    0      the planner decides
+ *    1, 2   the 128x128 kernels (fp32 or bf16-plane by prec) in their diagnostic staging forms
+ *           (store epilogue only; another epilogue runs the default form)
+ *    3      the ring kernels on any shape, never the eight-phase kernel
+ *    4      the 128x128 kernels
+ *    5, 7, 8 (once timing forms; tests pass them) the ring kernel at 256x256 tiles where the default
+ *           shape rules but the one-k-tile exclusion admit a 256-row kernel, with the split the
+ *           planner chose for its own tile
+ *    6      the eight-phase kernel on any shape where its 32-bit offsets fit (else: 13 on output
+ *           dimensions >= 128, the unsplit 256x256 ring tile below)
+ *    9      the fp32 VALU kernel (prec then 0); not in mvae_debug_epi
+ *    10     default shape rules, ring kernels only, accumulator-layout epilogue
+ *    11, 12 default shape rules, ring kernels only at tile N 128 / 256
+ *    13, 14 the eight-phase kernel on any shape where its 32-bit offsets fit, else the ring kernels
+ *    15     default shape rules, ring kernels only
+ * Any number but 0 keeps the step's
+ * wiring from choosing the VALU kernel, and only 0 lets A-as-bits prefer the eight-phase kernel. */
+enum { MVAE_KERNEL_F32 = 1, MVAE_KERNEL_VALU = 2, MVAE_KERNEL_PLANE = 3, MVAE_KERNEL_RING = 4,
+       MVAE_KERNEL_X3 = 5, MVAE_KERNEL_E8 = 6 };
+typedef struct mvae_plan_args {
+  int M, N, K, batch, at, bt;
+  int lda, ldb, ldc;
+  int prec, nA, nB, dynA;
+  int epi, c32, xdyn, padw;
+  int ld_aux, ldx, ldy;
+  int abits, x3;
+  int tm, split, valu, variant;
+  long long pA, pB, sA, sB, sC, pc;  /* plane and batch strides */
+  unsigned long long max_ws;
+  const void* Ap;
+  const void* Bp;
+  const void* C;
+  const void* cp;
+  const void* aux;
+  const void* auxp;
+  const void* x;
+  const void* xp;
+  const void* y;
+  const void* ws;
+} mvae_plan_args;
+typedef struct mvae_plan_out {
+  int kernel, staging, tm, tn, ntm, ntn, group, split, kchunk;
+  int lds_epilogue, vec_epilogue, epi_launched, valu_fits, refused;
+  unsigned long long ws_elems;
+} mvae_plan_out;
+int mvae_debug_plan(const mvae_plan_args* args, mvae_plan_out* out);
 
 #ifdef __cplusplus
 }

@@ -104,6 +104,26 @@ class mvae_epi_args(C.Structure):
                 ("y", C.c_void_p), ("rowpart", C.c_void_p), ("aux", C.c_void_p), ("auxp", C.c_void_p)]
 
 
+class mvae_plan_args(C.Structure):
+    """Arguments of ``mvae_debug_plan`` (``include/mvae.h``): everything a GEMM's kernel choice reads.
+    The pointers are never followed (only their alignment is read)."""
+    _fields_ = ([(n, C.c_int) for n in ("M", "N", "K", "batch", "at", "bt", "lda", "ldb", "ldc", "prec", "nA", "nB",
+                                        "dynA", "epi", "c32", "xdyn", "padw", "ld_aux", "ldx", "ldy", "abits", "x3",
+                                        "tm", "split", "valu", "variant")] +
+                [(n, C.c_longlong) for n in ("pA", "pB", "sA", "sB", "sC", "pc")] + [("max_ws", C.c_ulonglong)] +
+                [(n, C.c_void_p) for n in ("Ap", "Bp", "C", "cp", "aux", "auxp", "x", "xp", "y", "ws")])
+
+
+class mvae_plan_out(C.Structure):
+    """What ``mvae_debug_plan`` reports: the kernel (``KERNEL_NAMES``) and its launch plan."""
+    _fields_ = ([(n, C.c_int) for n in ("kernel", "staging", "tm", "tn", "ntm", "ntn", "group", "split", "kchunk",
+                                        "lds_epilogue", "vec_epilogue", "epi_launched", "valu_fits", "refused")] +
+                [("ws_elems", C.c_ulonglong)])
+
+
+KERNEL_NAMES = {1: "f32", 2: "valu", 3: "plane", 4: "ring", 5: "x3", 6: "e8"}
+
+
 class mvae_tensor(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("data", C.c_void_p), ("rows", C.c_int),
                 ("cols", C.c_int), ("ld", C.c_int), ("trained_by", C.c_int)]
@@ -204,6 +224,7 @@ _SIGS = {
                           C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_void_p], C.c_int),
     "mvae_debug_head": ([C.POINTER(mvae_head_args), C.c_void_p], C.c_int),
     "mvae_debug_epi": ([C.POINTER(mvae_epi_args), C.c_void_p], C.c_int),
+    "mvae_debug_plan": ([C.POINTER(mvae_plan_args), C.POINTER(mvae_plan_out)], C.c_int),
 }
 
 EXPORTED = tuple(_SIGS)

@@ -863,7 +863,7 @@ template <int EPI, bool TE>
 hipError_t launch_x_t(const PParams& p, bool at, bool bt, hipStream_t st) {
   const int nwg = p.g.ntm * p.g.ntn * p.g.batch * p.g.split;
   const dim3 g(nwg), b(WNT);
-  if (p.g.tn == 256) {  // (x3_serves: 256-row tiles)
+  if (p.g.tn == 256) {  // (the plane-stacked 256x256 form)
     if (!at && !bt) hipLaunchKernelGGL((gemm_bf16xw_kernel<false, false, EPI, TE>), g, b, 0, st, p);
     else if (at && !bt) hipLaunchKernelGGL((gemm_bf16xw_kernel<true, false, EPI, TE>), g, b, 0, st, p);
     else if (!at && bt) hipLaunchKernelGGL((gemm_bf16xw_kernel<false, true, EPI, TE>), g, b, 0, st, p);
@@ -885,51 +885,13 @@ hipError_t launch_x_t(const PParams& p, bool at, bool bt, hipStream_t st) {
   return hipGetLastError();
 }
 
-// the plane-stacked kernel serves this ring plan: option x3, tile N 128, the six f32x pairs of
-// three-plane operands (A's residual planes possibly zero at run time: its three-pair loop)
-bool x3_serves(const PParams& p) {
-  if (!p.x3 || p.npairs != 6) return false;
-  if (p.g.tn != 128 && !(p.g.tn == 256 && p.g.tm == 256 && p.x3 >= 2)) return false;
-  // (the 256x256 form's BCE instantiations spill: the head keeps the eight-phase / ring kernels)
-  if (p.g.tn == 256 && (p.g.epi.mode == EPI_BCE || p.g.epi.mode == EPI_BCEB)) return false;
-  for (int i = 0; i < 6; ++i)
-    if (p.pa[i] != x3_pa(3, 3, i) || p.pb[i] != x3_pb(3, 3, i)) return false;
-  return !p.dyn || p.npairs0 == 3;
-}
-
-// the row-major 16-B epilogue (epilogue_wide) applies: bases and strides keep every 8-column
-// chunk of every operand it touches 16-B aligned
-bool wide_epi_vec_ok(const Params& g) {
-  auto al = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-  const GemmEpi& e = g.epi;
-  if (e.c32 && (!al(g.C) || (g.ldc & 3) || (g.sC & 3))) return false;
-  if (e.cp && (!al(e.cp) || (g.ldc & 7) || (g.sC & 7) || (e.pc & 7))) return false;
-  if (e.mode == EPI_DACT && !e.auxp && (!al(e.aux) || (e.ld_aux & 3))) return false;
-  if (e.mode == EPI_DACT && e.auxp && (!al(e.auxp) || (e.ld_aux & 7))) return false;
-  if (e.mode == EPI_BCE || e.mode == EPI_BCEB) {
-    if (e.x && (!al(e.x) || (e.ldx & 3))) return false;
-    if (e.xp && (!al(e.xp) || (e.ldx & 7))) return false;
-    if (e.y && (!al(e.y) || (e.ldy & 3))) return false;
-  }
-  return true;
-}
-
-// The planned 256-row kernel: the eight-phase kernel (tile N = TN_E8, gemm_bf16e.hip) or the
-// interleaved ring kernel. Their epilogue goes through LDS (row-major 16-B stores) when the tile
-// writes bf16 planes or is the BCE head (2-B plane stores and 4-B target loads per element
-// otherwise), and stays in the C/D layout for fp32-only outputs (split-K slabs: 128-B row
-// segments already, where the LDS round trip measured 5-10 % slower); the eight-phase kernel's
-// accumulators are not in the C/D row-segment order, so its epilogue always goes through LDS
-// (variant 14 = 13); variant 10 keeps the ring kernel on the C/D layout.
+// The planned 256-row kernel (gemm_plan.cpp): the eight-phase kernel (gemm_bf16e.hip), the
+// plane-stacked kernel or the interleaved ring kernel, with the epilogue form the plan chose
 template <int EPI>
-hipError_t launch_wide(const PParams& p, bool at, bool bt, int variant, hipStream_t st) {
-  constexpr bool BCE = EPI == EPI_BCE || EPI == EPI_BCEB;
-  if (p.g.tn == TN_E8) {  // always the LDS epilogue: 16-B accesses where aligned, else element-wise
-    (void)variant;
-    return gemm_bf16e_launch(p, at, bt, EPI, wide_epi_vec_ok(p.g), st);
-  }
-  const bool te = (p.g.epi.cp || BCE) && variant != 10 && wide_epi_vec_ok(p.g);
-  if (x3_serves(p)) return te ? launch_x_t<EPI, true>(p, at, bt, st) : launch_x_t<EPI, false>(p, at, bt, st);
+hipError_t launch_wide(const PParams& p, bool at, bool bt, const GemmPlan& pl, hipStream_t st) {
+  if (pl.kernel == K_E8) return gemm_bf16e_launch(p, at, bt, EPI, pl.vec_epilogue, st);
+  const bool te = pl.lds_epilogue;
+  if (pl.kernel == K_X3) return te ? launch_x_t<EPI, true>(p, at, bt, st) : launch_x_t<EPI, false>(p, at, bt, st);
   if (te) return launch_q_t<EPI, true>(p, at, bt, st);
   return launch_q_t<EPI, false>(p, at, bt, st);
 }
@@ -949,131 +911,22 @@ hipError_t launch_layout(const PParams& p, bool at, bool bt, hipStream_t st) {
   return launch_t<true, true, EPI, BK, DB>(p, st);
 }
 
-// variant (diagnostics): 0 = single-buffered BK 64 (default: 40 KB LDS, 2-3 WGs/CU),
+// staging (diagnostics): 0 = single-buffered BK 64 (default: 40 KB LDS, 2-3 WGs/CU),
 // 1 = double-buffered BK 32, 2 = double-buffered BK 64 (80 KB LDS: one workgroup per CU).
 // Measured on the C2 shapes (profiles/r1/gemm_ab_bf16_variants.txt): BK-64 single buffer
 // fastest everywhere (e.g. 308 vs 274 vs 179 TF/s on the layer-0 forward).
 template <int EPI>
-hipError_t launch_var(const PParams& p, bool at, bool bt, int variant, hipStream_t st) {
+hipError_t launch_var(const PParams& p, bool at, bool bt, int staging, hipStream_t st) {
   if constexpr (EPI == EPI_STORE) {
-    if (variant == 1) return launch_layout<EPI, 32, true>(p, at, bt, st);
-    if (variant == 2) return launch_layout<EPI, 64, true>(p, at, bt, st);
+    if (staging == 1) return launch_layout<EPI, 32, true>(p, at, bt, st);
+    if (staging == 2) return launch_layout<EPI, 64, true>(p, at, bt, st);
   }
   return launch_layout<EPI, 64, false>(p, at, bt, st);
 }
 
 }  // namespace
 
-bool gemm_bf16_wide(const GemmDesc& d) {
-  if (d.prec == GEMM_F32) return false;
-  // 10-12, 15: default-shape variants of the ring kernel (C/D epilogue, forced tile N, no
-  // eight-phase kernel); 3: the ring kernel, 6 / 13 / 14: the eight-phase kernel, on any shape
-  const int v = (d.variant >= 10 && d.variant != 13 && d.variant != 14) ? 0 : d.variant;
-  if (v == 1 || v == 2 || v == 4) return false;  // 128x128 register-staged variants
-  // output dimensions >= 128 (the thin decoder / latent-head GEMMs of C3-C5: a 256-row ring
-  // tile ran them 1.6-1.7x faster than the 128x128 register-staged kernel, profiles/r4/README.md)
-  if (v != 3 && v != 6 && v != 13 && v != 14 && (d.M < 128 || d.N < 128)) return false;
-  // one k-tile and under a CU's worth of 256x256 tiles (dec layer 1: K = L + 1; the head's
-  // dgrad: K = 2L): epilogue-bound on few CUs, the 128x128 kernels spread it wider
-  const long long t256 = (long long)((d.M + 255) / 256) * ((d.N + 255) / 256) * d.batch;
-  if (v == 0 && d.K <= 64 && t256 < 256) return false;
-  auto a8 = [](long long v) { return (v & 7) == 0; };
-  if (!a8(d.lda) || !a8(d.ldb) || !a8(d.pA) || !a8(d.pB)) return false;
-  if (d.batch > 1 && (!a8(d.sA) || !a8(d.sB))) return false;
-  if ((reinterpret_cast<uintptr_t>(d.Ap) | reinterpret_cast<uintptr_t>(d.Bp)) & 15) return false;
-  return true;
-}
-
-// Joint choice of the kernel (256 x 256 eight-phase kernel; 256 x 256 / 256 x 128 / 192 x 256 /
-// 192 x 128 ring kernels) and split-K: each kernel's time is its rounds of resident workgroups
-// (one per CU) x (k-tiles + fixed prologue/epilogue cost) x its time per k-tile; split-K adds the
-// fp32 slab round trip and the reduction launch. Variants 11 / 12 force the ring kernel at tile
-// N 128 / 256, 13 / 14 the eight-phase kernel, 15 the ring kernels only.
-struct WidePlan { int split = 1; int tn = 256; int tm = 256; };
-static WidePlan wide_plan(const GemmDesc& d, size_t max_ws) {
-  const bool fixed = d.epi.mode == EPI_BCE || d.epi.mode == EPI_BCEB || d.epi.mode == EPI_SIGMOID;
-  const int kt = (d.K + 63) / 64;
-  const bool x3 = d.x3 && d.prec == GEMM_F32X && d.nA == 3 && d.nB == 3;
-  const int T = d.nA > d.nB ? d.nA : d.nB;
-  int np = 0;
-  for (int i = 0; i < d.nA; ++i)
-    for (int j = 0; j < d.nB; ++j) np += i + j < T;
-  if (d.dynA) np = (np + (d.nB < T ? d.nB : T)) / 2;  // A's residual planes often all zero
-  const bool big = d.M >= 256 && d.N >= 256;
-  const bool force_e8 = d.variant == 13 || d.variant == 14 || d.variant == 6;
-  // the eight-phase kernel where it measured faster than the ring kernels (profiles/r4): enough
-  // 256x256 tiles to fill the chip, or a long k-loop over >= 32 tiles; its (k-tile, pair)
-  // iterations copy both operand images (the ring kernel reuses an unchanged image)
-  const long long t256 = (long long)((d.M + 255) / 256) * ((d.N + 255) / 256) * d.batch;
-  // 192-row ring tiles: k-contiguous A, epilogues other than the BCE head / sigmoid
-  const bool t192 = !d.at && d.epi.mode != EPI_BCE && d.epi.mode != EPI_BCEB &&
-                    d.epi.mode != EPI_SIGMOID;
-  const long long tl192 = (long long)((d.M + 191) / 192) * ((d.N + 255) / 256) * d.batch;
-  // ... except (in-step A/B, profiles/r4/README.md) single-product GEMMs where one round of
-  // 192-row ring tiles keeps >= 4/3 as many CUs busy (C3 layer-0 forward: 256 vs 192 workgroups,
-  // 0.255 vs 0.276 ms; hidden forward 31.7 vs 32.7 us)
-  // (a real one-round fill: not a tile count split-K multiplies anyway -- the C3 decoder-output
-  // dgrad, 86 vs 64 tiles, stays on the eight-phase kernel: 0.107 vs 0.115 ms in r4n)
-  const bool ring_fills = t192 && np == 1 && tl192 > 128 && tl192 <= 256 && 3 * tl192 >= 4 * t256;
-  const bool e8_rule = big && t256 >= 32 && (t256 >= 256 || (long long)np * kt >= 64) && !ring_fills;
-  // the eight-phase kernel addresses an operand plane by 32-bit per-lane element offsets
-  const long long ea = (long long)(d.at ? d.K : d.M) * d.lda, eb = (long long)(d.bt ? d.N : d.K) * d.ldb;
-  const bool e8_fits = ea < (1LL << 32) && eb < (1LL << 32);
-  // A as bits (a 0/1 operand): the eight-phase kernel, whose bits path reads it (its plane path
-  // runs the rare batch with another pixel value)
-  const bool allow_e8 = e8_fits && (force_e8 || (d.variant == 0 && (e8_rule || d.Abits)));
-  double best = 1e30;
-  WidePlan pl;
-  for (int cand = 0; cand < 5; ++cand) {
-    // candidates: ring 256x256, 256x128, eight-phase 256x256, ring 192x256, 192x128
-    const bool e8 = cand == 2;
-    const int w = cand == 0 || cand == 3 ? 256 : cand == 1 || cand == 4 ? 128 : TN_E8;
-    const int tmr = cand >= 3 ? 192 : 256;
-    if (e8 ? !allow_e8 : allow_e8 || (force_e8 && e8_fits)) continue;
-    if (!e8 && d.Abits && e8_fits && d.variant == 0) continue;
-    if (cand >= 3 && !t192) continue;
-    if ((d.tm == 192 && t192 && cand != 3 && cand != 4) || (d.tm == 256 && cand >= 3)) continue;
-    if (d.variant == 11 && w != 128) continue;
-    if (d.variant == 12 && w != 256) continue;
-    if (!e8 && (d.M < 128 || d.N < 128) && d.variant != 3 && d.variant < 10) continue;
-    const int tnn = e8 ? 256 : w;
-    const long long tiles = (long long)((d.M + tmr - 1) / tmr) * ((d.N + tnn - 1) / tnn) * d.batch;
-    // ring kernels, measured: 4096^3 at 1.06 PF/s = 1.94 us per 256x256 k-tile per CU; the
-    // 256x128 tile does half the MFMA work per k-tile in ~1.5 us (profiles/r2/gemm_ab_tile_n.txt);
-    // 192-row tiles interpolated (a fixed ~1.1 us per k-tile plus ~0.1 us per 32x32 block).
-    // eight-phase kernel: per 256x256 k-tile (gemm_bf16e.hip)
-    double t_kt = e8 ? 1.35e-6 : tmr == 192 ? (w == 256 ? 1.7e-6 : 1.4e-6) : (w == 256 ? 1.9e-6 : 1.5e-6);
-    // the plane-stacked kernel (option x3) serves the six-pair f32x ring plans at tile N 128:
-    // C2 hidden forward 60 -> 50 us, hidden dgrad 72 -> 67 us in the region pass (r6zi)
-    if (x3 && !e8 && w == 128) t_kt *= 0.88;
-    const double fix = 3.0;
-    for (int s = 1; s <= (fixed ? 1 : 32); ++s) {
-      if (s > 1 && kt / s < 2) break;
-      if (s > 1 && (size_t)d.batch * s * d.M * d.N > max_ws) break;
-      const double rounds = std::ceil(tiles * s / 256.0);
-      double t = rounds * (np * std::ceil((double)kt / s) + fix) * t_kt;
-      // split-K: the slabs' write + read and the reduction launch (8 us fixed: C2's f32x hidden
-      // forward, 12288 x 500 x 501, ran 65.6 us at 192x256 split 2 against 61.0 us as one round
-      // of 192x128 tiles unsplit, where the model with 4 us preferred the split, r5zq)
-      if (s > 1) t += (double)d.batch * s * d.M * d.N * 8.0 / 4.5e12 + 8e-6;
-      if (t < best * 0.97) { best = t; pl.split = s; pl.tn = w; pl.tm = tmr; }
-    }
-  }
-  return pl;
-}
-
-int gemm_bf16_wide_split(const GemmDesc& d, size_t max_ws) { return wide_plan(d, max_ws).split; }
-
-int gemm_bf16_wide_tn(const GemmDesc& d, size_t max_ws) { return wide_plan(d, max_ws).tn; }
-
-int gemm_bf16_wide_tm(const GemmDesc& d, size_t max_ws) { return wide_plan(d, max_ws).tm; }
-
-void gemm_bf16_wide_plan(const GemmDesc& d, size_t max_ws, int* split, int* tn, int* tm) {
-  const WidePlan pl = wide_plan(d, max_ws);
-  *split = pl.split; *tn = pl.tn; *tm = pl.tm;
-}
-
-hipError_t gemm_bf16_launch(const gemm::Params& g, const GemmDesc& d, int epi, hipStream_t st) {
+hipError_t gemm_bf16_launch(const gemm::Params& g, const GemmDesc& d, const GemmPlan& pl, hipStream_t st) {
   PParams p;
   p.g = g;
   p.A = d.Ap; p.pA = d.pA;
@@ -1084,11 +937,6 @@ hipError_t gemm_bf16_launch(const gemm::Params& g, const GemmDesc& d, int epi, h
   p.abits = d.Abits; p.abits_kts = d.abits_kts; p.abits_sb = d.abits_sb; p.anb = d.anb;
   p.bits_reg = d.bits_reg;
   p.x3 = d.x3;
-  // tile order: bands of 8 m-tiles walked n by n when a row has >= 8 n-tiles, so the 32 tiles
-  // an XCD holds at once share 8 A and 4 B tiles in its L2 (C5 latent-head forward
-  // 24576 x 4000 x 501: 0.177 -> 0.161 ms; neutral on the BCE head and the other shapes,
-  // profiles/r4/r4u_tile_group.txt); GemmDesc::group >= 0 overrides (A/B: mvae_bench_gemm)
-  const int tile_group = d.group;
   // plane pairs (i, j), i + j < max(nA, nB); the pairs with i = 0 first, j snaking (ascending for
   // even i, descending for odd i): (0,0) (0,1) (0,2) (1,1) (1,0) (2,0), so consecutive pairs share
   // the B plane at both A-plane changes and the ring kernel copies 3 A + 5 B images per k-tile
@@ -1110,34 +958,25 @@ hipError_t gemm_bf16_launch(const gemm::Params& g, const GemmDesc& d, int epi, h
   // launch then sums in another order than its 256x128 ring-tile remainder, bce_split: the same
   // values to fp32 rounding)
   p.reuse = n > 1;
-  if (gemm_bf16_wide(d)) {
-    // tile N: the planner's (gemm_run), 256 for the diagnostic variants of the 256x256 forms
-    const bool q = d.variant == 0 || d.variant == 3 || d.variant == 6 || (d.variant >= 10 && d.variant <= 15);
-    p.g.tn = q && (g.tn == 128 || g.tn == TN_E8) ? g.tn : 256;
-    p.g.tm = q && p.g.tn != TN_E8 && g.tm == 192 && !d.at ? 192 : 256;
-    const int tm = p.g.tm, tn = p.g.tn == TN_E8 ? 256 : p.g.tn;
-    p.g.ntm = (d.M + tm - 1) / tm;
-    p.g.ntn = (d.N + tn - 1) / tn;
-    p.g.group = tile_group >= 0 ? tile_group : (p.g.ntn >= 8 ? 8 : 0);
-    switch (epi) {
-      case EPI_STORE: return launch_wide<EPI_STORE>(p, d.at, d.bt, d.variant, st);
-      case EPI_ACT: return launch_wide<EPI_ACT>(p, d.at, d.bt, d.variant, st);
-      case EPI_DACT:
-        return d.epi.auxp ? launch_wide<EPI_DACTB>(p, d.at, d.bt, d.variant, st)
-                          : launch_wide<EPI_DACT>(p, d.at, d.bt, d.variant, st);
-      case EPI_BCE: return launch_wide<EPI_BCE>(p, d.at, d.bt, d.variant, st);
-      case EPI_BCEB: return launch_wide<EPI_BCEB>(p, d.at, d.bt, d.variant, st);
-      case EPI_SIGMOID: return launch_wide<EPI_SIGMOID>(p, d.at, d.bt, d.variant, st);
+  if (gemm_wide_kernel(pl.kernel)) {
+    switch (pl.epi_launched) {
+      case EPI_STORE: return launch_wide<EPI_STORE>(p, d.at, d.bt, pl, st);
+      case EPI_ACT: return launch_wide<EPI_ACT>(p, d.at, d.bt, pl, st);
+      case EPI_DACT: return launch_wide<EPI_DACT>(p, d.at, d.bt, pl, st);
+      case EPI_DACTB: return launch_wide<EPI_DACTB>(p, d.at, d.bt, pl, st);
+      case EPI_BCE: return launch_wide<EPI_BCE>(p, d.at, d.bt, pl, st);
+      case EPI_BCEB: return launch_wide<EPI_BCEB>(p, d.at, d.bt, pl, st);
+      case EPI_SIGMOID: return launch_wide<EPI_SIGMOID>(p, d.at, d.bt, pl, st);
       default: return hipErrorInvalidValue;
     }
   }
-  switch (epi) {
-    case EPI_STORE: return launch_var<EPI_STORE>(p, d.at, d.bt, d.variant, st);
-    case EPI_ACT: return launch_var<EPI_ACT>(p, d.at, d.bt, d.variant, st);
-    case EPI_DACT: return launch_var<EPI_DACT>(p, d.at, d.bt, d.variant, st);
-    case EPI_BCE: return launch_var<EPI_BCE>(p, d.at, d.bt, d.variant, st);
-    case EPI_BCEB: return launch_var<EPI_BCEB>(p, d.at, d.bt, d.variant, st);
-    case EPI_SIGMOID: return launch_var<EPI_SIGMOID>(p, d.at, d.bt, d.variant, st);
+  switch (pl.epi_launched) {
+    case EPI_STORE: return launch_var<EPI_STORE>(p, d.at, d.bt, pl.staging, st);
+    case EPI_ACT: return launch_var<EPI_ACT>(p, d.at, d.bt, pl.staging, st);
+    case EPI_DACT: return launch_var<EPI_DACT>(p, d.at, d.bt, pl.staging, st);
+    case EPI_BCE: return launch_var<EPI_BCE>(p, d.at, d.bt, pl.staging, st);
+    case EPI_BCEB: return launch_var<EPI_BCEB>(p, d.at, d.bt, pl.staging, st);
+    case EPI_SIGMOID: return launch_var<EPI_SIGMOID>(p, d.at, d.bt, pl.staging, st);
     default: return hipErrorInvalidValue;
   }
 }

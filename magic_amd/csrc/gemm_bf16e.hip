@@ -71,7 +71,7 @@ __device__ __attribute__((aligned(16))) unsigned short g_zero16[8] = {0, 0, 0, 0
 // Chunks past K read g_zero16 (both operands, so the tail products are exact zeros).
 template <bool KC>
 struct HLoad {
-  unsigned voff[2][2];  // [j][h] element offsets (a plane of < 2^32 elements: gemm_bf16_wide)
+  unsigned voff[2][2];  // [j][h] element offsets (a plane of < 2^32 elements: gemm_plan.cpp e8_fits)
   int kc[2];            // the chunk's k within the tile (KC: first k of its 8; else its k-row)
   __device__ __forceinline__ void init(int ld, int r0, int nrows, int wave, int lane) {
 #pragma unroll
@@ -704,7 +704,7 @@ hipError_t launch_bits_from_plane(const unsigned short* plane, int ld, bool tran
   return hipGetLastError();
 }
 
-// the eight-phase kernel for a planned 256 x 256 tile (PParams::g.tn == TN_E8): te = the row-major
+// the eight-phase kernel for a planned 256 x 256 tile (GemmPlan::kernel == K_E8): te = the row-major
 // LDS epilogue with 16-B global accesses, else element-wise
 hipError_t gemm_bf16e_launch(const PParams& p, bool at, bool bt, int epi, bool te, hipStream_t st) {
   switch (epi) {

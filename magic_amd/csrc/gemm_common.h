@@ -20,13 +20,12 @@ struct Params {
   long long sA, sB, sC;     // batch strides
   int batch, split, kchunk;
   int ntm, ntn;
-  int tn;                   // bf16 DMA kernels: ring-kernel tile N (256 or 128) or TN_E8
+  int tn;                   // bf16 DMA kernels: tile N (ring kernel: 256 or 128)
   int tm = 256;             // ... and ring-kernel tile M (256, or 192 for a k-contiguous A)
   int group = 0;            // tile order: 0 = row by row (n fastest); G > 0 = bands of G m-tiles
                             // walked n by n, so an XCD's resident tiles share A and B in its L2
   GemmEpi epi;
 };
-constexpr int TN_E8 = GEMM_TN_E8;  // Params::tn of the 256 x 256 eight-phase kernel (gemm_bf16e.hip)
 
 // launch parameters of the bf16-plane kernels (gemm_bf16.hip, gemm_bf16e.hip)
 struct PParams {
@@ -334,7 +333,7 @@ __device__ __forceinline__ void epilogue_g(const Params& p, const Tile& t, f32x1
 // operands (DACT aux, BCE target), the math, and 16-B stores of the fp32 output and of each
 // bf16 plane. BCE row partials: each 8-column chunk's terms summed in order, then a fixed xor
 // tree over the 16 lanes of a 128-column block; lane 0 of the 16 writes rowpart. Requires
-// (wide_epi_vec_ok) 16-B aligned bases and ld / plane / batch strides that keep 8-column chunks
+// (GemmPlan::vec_epilogue) 16-B aligned bases and ld / plane / batch strides that keep 8-column chunks
 // 16-B aligned; chunks that cross N fall back to element stores.
 __device__ __forceinline__ void ld8f(const float* p, float (&v)[8]) {
   const float4 a = *reinterpret_cast<const float4*>(p);
@@ -379,7 +378,7 @@ __device__ __forceinline__ void st8_planes(unsigned short* cp, long long pc, int
 // tools/micro/epi.hip)
 // Generic form: write_band(band, mi) writes this wave's part of band mi (row-major, TW floats
 // per band row) from its accumulators in whatever MFMA layout they are; vec = false: every
-// global access element-wise (bases / strides not 16-B aligned, wide_epi_vec_ok false).
+// global access element-wise (bases / strides not 16-B aligned, GemmPlan::vec_epilogue false).
 // RMAP: tile row of band row br of band mi -- 0: wave row (br >> 5) owns rows [64 MI wr, +64 MI)
 // and band mi is its 32-row block mi; 1 (eight-phase kernel, MI 4): 32-row block mi of wave row
 // wr is tile rows 128 (mi >> 1) + 64 wr + 32 (mi & 1)
@@ -676,7 +675,7 @@ __device__ __forceinline__ void epilogue(const Params& p, const Tile& t, f32x16 
 
 }  // namespace gemm
 
-// the eight-phase 256 x 256 kernel (gemm_bf16e.hip) for a planned tile (g.tn == TN_E8); te: the
+// the eight-phase 256 x 256 kernel (gemm_bf16e.hip) for a planned tile (GemmPlan::kernel == K_E8); te: the
 // row-major LDS epilogue
 hipError_t gemm_bf16e_launch(const gemm::PParams& p, bool at, bool bt, int epi, bool te, hipStream_t st);
 

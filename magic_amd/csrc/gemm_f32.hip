@@ -27,6 +27,7 @@ namespace {
 
 using namespace gemm;
 constexpr int BK = 32;
+static_assert(BM == PLAN_T128 && BN == PLAN_T128 && BK == PLAN_BK_F32, "gemm_plan counts in these tiles");
 
 template <bool KCONTIG, int SLD, int ROWS>
 struct TileLoader;
@@ -104,7 +105,7 @@ struct TileLoader<false, SLD, ROWS> {
   }
 };
 
-// VAR (diagnostic A/B variants, EPI_STORE only): 0 default; 1 fragments read per k-step
+// VAR (GemmForce::staging, diagnostic A/B forms, EPI_STORE only): 0 default; 1 fragments read per k-step
 // (no read-ahead); 2 no XCD remap.
 template <bool AT, bool BT, int EPI, int VAR = 0>
 __global__ __launch_bounds__(NT, 2) void gemm_f32_kernel(Params p) {
@@ -327,8 +328,8 @@ hipError_t launch_layout(const Params& p, bool at, bool bt, hipStream_t st) {
   return launch_t<true, true, EPI, VAR>(p, st);
 }
 
-hipError_t launch_store(const Params& p, bool at, bool bt, int variant, hipStream_t st) {
-  switch (variant) {
+hipError_t launch_store(const Params& p, bool at, bool bt, int staging, hipStream_t st) {
+  switch (staging) {
     case 1: return launch_layout<EPI_STORE, 1>(p, at, bt, st);
     case 2: return launch_layout<EPI_STORE, 2>(p, at, bt, st);
     default: return launch_layout<EPI_STORE, 0>(p, at, bt, st);
@@ -339,88 +340,51 @@ hipError_t launch_store(const Params& p, bool at, bool bt, int variant, hipStrea
 
 int gemm_bce_nblk(int N) { return (N + BN - 1) / BN; }
 
-int gemm_plan_split(const GemmDesc& d, size_t max_ws) {
-  if (d.epi.mode == EPI_BCE || d.epi.mode == EPI_BCEB || d.epi.mode == EPI_SIGMOID) return 1;
-  if (d.valu) return gemm_valu_split(d, max_ws);
-  if (gemm_bf16_wide(d)) return gemm_bf16_wide_split(d, max_ws);
-  const int ntm = (d.M + BM - 1) / BM, ntn = (d.N + BN - 1) / BN;
-  const long long tiles = (long long)ntm * ntn * d.batch;
-  const int ktiles = (d.K + BK - 1) / BK;
-  // Throughput model: each CU works through ceil(WGs/256) workgroups (two co-resident WGs
-  // overlap each other's stalls but share the MFMA pipes), each WG costs its k-tiles plus a
-  // fixed prologue/epilogue; split-K adds the slab round trip and one reduction launch.
-  const double cus = 256.0;
-  // one 128x128x32 k-tile per CU: fp32 MFMA rate; bf16 / 3-term split are load-bound
-  const double t_ktile = d.prec == GEMM_F32 ? 1.75e-6 : (d.prec == GEMM_BF16 ? 0.3e-6 : 0.5e-6);
-  double best = 1e30;
-  int best_s = 1;
-  for (int s = 1; s <= 32; ++s) {
-    if (s > 1 && ktiles / s < 4) break;
-    if (s > 1 && (size_t)d.batch * s * d.M * d.N > max_ws) break;
-    const double rounds = std::ceil(tiles * s / cus);
-    double t = rounds * ((double)ktiles / s + 2.0) * t_ktile;
-    if (s > 1) t += (double)d.batch * s * d.M * d.N * 8.0 / 4.5e12 + 4e-6;
-    if (t < best * 0.97) { best = t; best_s = s; }
-  }
-  return best_s;
-}
-
-size_t gemm_workspace_elems(const GemmDesc& d) {
-  const int s = d.split > 0 ? d.split : gemm_plan_split(d, ~size_t(0));
-  return s > 1 ? (size_t)d.batch * s * d.M * d.N : 0;
-}
-
 hipError_t gemm_run(const GemmDesc& d, float* ws, size_t ws_elems, hipStream_t st) {
   if (d.M <= 0 || d.N <= 0) return hipSuccess;
+  // one planner pass: kernel, tile, grid, split-K, epilogue form
+  const GemmPlan pl = gemm_plan(d, ws ? ws_elems : 0, (reinterpret_cast<uintptr_t>(ws) & 15) == 0);
+  const int split = pl.split;
+  if (gemm_plan_refused(pl, ws != nullptr, ws_elems)) return hipErrorInvalidValue;
   Params p;
   p.M = d.M; p.N = d.N; p.K = d.K;
   p.A = d.A; p.lda = d.lda; p.B = d.B; p.ldb = d.ldb;
   p.sA = d.sA; p.sB = d.sB;
   p.batch = d.batch;
-  p.ntm = (d.M + BM - 1) / BM; p.ntn = (d.N + BN - 1) / BN;
+  p.ntm = pl.ntm; p.ntn = pl.ntn;
+  p.tm = pl.tm; p.tn = pl.tn; p.group = pl.group;
+  p.split = split; p.kchunk = pl.kchunk;
   p.epi = d.epi;
   if (d.prec == GEMM_F32) p.epi.xdyn = nullptr;  // fp32 kernels read the fp32 BCE target
-  // one planner pass: split-K and (bf16 DMA kernels) the ring tile
-  const size_t wsz = ws ? ws_elems : 0;
-  int split = 1;
-  p.tn = 0;
-  p.tm = 256;
-  if (!d.valu && gemm_bf16_wide(d)) gemm_bf16_wide_plan(d, wsz, &split, &p.tn, &p.tm);
-  else split = gemm_plan_split(d, wsz);
-  if (d.split > 0) split = d.split;
-  if (split > 1 && (!ws || (size_t)d.batch * split * d.M * d.N > ws_elems)) return hipErrorInvalidValue;
-  p.split = split;
-  const int kb = d.prec == GEMM_F32 ? BK : 64;  // k-tile of the kernel that runs
-  const int ktiles = (d.K + kb - 1) / kb;
-  p.kchunk = ((ktiles + split - 1) / split) * kb;
   if (split == 1) {
     p.C = d.C; p.ldc = d.ldc; p.sC = d.sC;
-    if (d.valu) return gemm_valu_launch(p, d, d.epi.mode, st);
-    if (d.prec != GEMM_F32) {
-      // BCE with a bf16-plane target: one launch choosing the plane or the fp32 target by *xdyn
-      if (d.epi.mode == EPI_BCE && d.epi.xp && d.epi.xdyn) return gemm_bf16_launch(p, d, EPI_BCEB, st);
-      Params q = p;
-      q.epi.xdyn = nullptr;  // a single BCE launch always runs (fp32 target)
-      return gemm_bf16_launch(q, d, d.epi.mode, st);
-    }
-    switch (d.epi.mode) {
-      case EPI_STORE: return launch_store(p, d.at, d.bt, d.variant, st);
-      case EPI_ACT: return launch_layout<EPI_ACT>(p, d.at, d.bt, st);
-      case EPI_DACT: return launch_layout<EPI_DACT>(p, d.at, d.bt, st);
-      case EPI_BCE: return launch_layout<EPI_BCE>(p, d.at, d.bt, st);
-      case EPI_SIGMOID: return launch_layout<EPI_SIGMOID>(p, d.at, d.bt, st);
-      default: return hipErrorInvalidValue;
+    // a plane kernel's launch reads the fp32 BCE target unless the planner substituted EPI_BCEB, the
+    // form chosen at run time (a caller never sets that mode itself; if one did, the fp32 target too)
+    const bool chooses = d.epi.mode == EPI_BCE && pl.epi_launched == EPI_BCEB;
+    if (pl.kernel >= K_PLANE && !chooses) p.epi.xdyn = nullptr;
+  } else {
+    // split-K: raw slabs [batch][split][M][N], then ordered reduction + epilogue
+    p.C = ws; p.ldc = d.N; p.sC = (long long)d.M * d.N;
+    p.epi.cp = nullptr;  // planes (and the fp32 output, if any) are written by the reduction
+    p.epi.c32 = 1;       // the slabs themselves always
+    p.epi.padw = 0;      // slab rows are N wide (ldc = N): no whole-chunk stores past column N
+  }
+  hipError_t err = hipErrorInvalidValue;
+  if (pl.kernel == K_VALU) {
+    err = gemm_valu_launch(p, d.at, d.bt, pl.epi_launched, st);
+  } else if (pl.kernel != K_F32) {
+    err = gemm_bf16_launch(p, d, pl, st);
+  } else {
+    switch (pl.epi_launched) {
+      case EPI_STORE: err = launch_store(p, d.at, d.bt, pl.staging, st); break;
+      case EPI_ACT: err = launch_layout<EPI_ACT>(p, d.at, d.bt, st); break;
+      case EPI_DACT: err = launch_layout<EPI_DACT>(p, d.at, d.bt, st); break;
+      case EPI_BCE: err = launch_layout<EPI_BCE>(p, d.at, d.bt, st); break;
+      case EPI_SIGMOID: err = launch_layout<EPI_SIGMOID>(p, d.at, d.bt, st); break;
+      default: break;
     }
   }
-  // split-K: raw slabs [batch][split][M][N], then ordered reduction + epilogue
-  p.C = ws; p.ldc = d.N; p.sC = (long long)d.M * d.N;
-  p.epi.cp = nullptr;  // planes (and the fp32 output, if any) are written by the reduction
-  p.epi.c32 = 1;       // the slabs themselves always
-  p.epi.padw = 0;      // slab rows are N wide (ldc = N): no whole-chunk stores past column N
-  hipError_t err = d.valu ? gemm_valu_launch(p, d, EPI_STORE, st)
-                 : d.prec != GEMM_F32 ? gemm_bf16_launch(p, d, EPI_STORE, st)
-                                      : launch_store(p, d.at, d.bt, d.variant, st);
-  if (err != hipSuccess) return err;
+  if (split == 1 || err != hipSuccess) return err;
   const long long total = (long long)d.M * d.N;
   int grid = (int)std::min<long long>((total + 255) / 256, 2048);
   dim3 g(grid, 1, d.batch);

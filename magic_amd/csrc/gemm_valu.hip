@@ -18,6 +18,7 @@ namespace {
 using namespace gemm;
 
 constexpr int VT = 64, VKC = 32, VNT = 256, VSLD = VT + 4;  // LDS row stride (16-B aligned rows)
+static_assert(VT == PLAN_VT && VKC == PLAN_VKC, "gemm_plan counts in these tiles");
 
 // chunk [k0, k0 + VKC) x [r0, r0 + VT) of an operand: 2 float4 per thread held in registers
 // (load) while the previous chunk is multiplied, then written to s[k][r] (store)
@@ -223,38 +224,12 @@ hipError_t launch_v_layout(const Params& p, bool at, bool bt, hipStream_t st) {
 
 }  // namespace
 
-bool gemm_valu_fits(const GemmDesc& d) {
-  if (d.variant != 0) return false;
-  if (d.epi.mode == EPI_BCE || d.epi.mode == EPI_BCEB) return false;
-  // skinny K, or a skinny output with a short K (the long-K weight gradients of the latent head
-  // and decoder layer 1 stay on the fp32 MFMA kernel: measured faster, profiles/r2)
-  const int lo = d.M < d.N ? d.M : d.N;
-  return d.K <= 64 || (lo <= 64 && d.K <= 1024);
-}
-
-int gemm_valu_split(const GemmDesc& d, size_t max_ws) {
-  const long long tiles = (long long)((d.M + VT - 1) / VT) * ((d.N + VT - 1) / VT) * d.batch;
-  const int chunks = (d.K + VKC - 1) / VKC;
-  // latency-bound small kernels: aim at >= 4 waves per SIMD (1024 workgroups of 4 waves), at
-  // least 2 chunks per slice, at most 16 slices (the ordered reduction reads them serially)
-  int s = 1;
-  while (s * 2 <= 16 && s * 2 <= chunks / 2 && tiles * s < 1024 &&
-         (size_t)d.batch * 2 * s * d.M * d.N <= max_ws)
-    s *= 2;
-  return s;
-}
-
-hipError_t gemm_valu_launch(const gemm::Params& g, const GemmDesc& d, int epi, hipStream_t st) {
-  Params p = g;
-  p.ntm = (d.M + VT - 1) / VT;
-  p.ntn = (d.N + VT - 1) / VT;
-  const int chunks = (d.K + VKC - 1) / VKC;
-  p.kchunk = ((chunks + p.split - 1) / p.split) * VKC;
+hipError_t gemm_valu_launch(const gemm::Params& p, bool at, bool bt, int epi, hipStream_t st) {
   switch (epi) {
-    case EPI_STORE: return launch_v_layout<EPI_STORE>(p, d.at, d.bt, st);
-    case EPI_ACT: return launch_v_layout<EPI_ACT>(p, d.at, d.bt, st);
-    case EPI_DACT: return launch_v_layout<EPI_DACT>(p, d.at, d.bt, st);
-    case EPI_SIGMOID: return launch_v_layout<EPI_SIGMOID>(p, d.at, d.bt, st);
+    case EPI_STORE: return launch_v_layout<EPI_STORE>(p, at, bt, st);
+    case EPI_ACT: return launch_v_layout<EPI_ACT>(p, at, bt, st);
+    case EPI_DACT: return launch_v_layout<EPI_DACT>(p, at, bt, st);
+    case EPI_SIGMOID: return launch_v_layout<EPI_SIGMOID>(p, at, bt, st);
     default: return hipErrorInvalidValue;
   }
 }

@@ -36,6 +36,33 @@ struct Arena {
 #define DIAG(expr) MV_TRY(nullptr, who, expr)
 bool misaligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
 
+// The kernel numbers of the ABI (mvae_debug_gemm, mvae_bench_gemm, mvae_debug_epi, mvae_debug_plan;
+// include/mvae.h has the table) as forces: the only place that knows the numbers. False: no such number.
+bool force_from_abi(int v, GemmForce* f) {
+  *f = GemmForce{};
+  switch (v) {
+    case 0: return true;
+    case 1: case 2: f->kernel = K_PLANE; f->staging = v; return true;
+    case 3: f->kernel = K_RING; f->any_shape = true; return true;
+    case 4: f->kernel = K_PLANE; return true;
+    case 5: case 7: case 8: f->kernel = K_RING; f->late_256 = true; return true;
+    case 6: f->kernel = K_E8; f->any_shape = true; f->ring_from_128 = true; return true;
+    case 9: f->kernel = K_VALU; return true;
+    case 10: f->kernel = K_RING; f->cd_epilogue = true; return true;
+    case 11: f->kernel = K_RING; f->tile_n = 128; return true;
+    case 12: f->kernel = K_RING; f->tile_n = 256; return true;
+    case 13: case 14: f->kernel = K_E8; f->any_shape = true; return true;
+    case 15: f->no_e8 = true; return true;
+    default: return false;
+  }
+}
+// ... into d; the VALU kernel is fp32 arithmetic
+bool force_desc(int v, GemmDesc* d) {
+  if (!force_from_abi(v, &d->force)) return false;
+  if (d->force.kernel == K_VALU) d->prec = GEMM_F32;
+  return true;
+}
+
 // mvae_bench_gemm's epilogue (variant >> 8): the step's fused epilogues with their operand reads
 // and the output planes the next GEMM would read (np planes of nc elements)
 int bench_epilogue(Arena& ar, GemmDesc& d, int epi, int np, size_t nc) {
@@ -164,9 +191,8 @@ extern "C" int mvae_debug_gemm(int M, int N, int K, const float* A, int lda, int
   Arena ar(st);
   GemmDesc d = gd(M, N, K, A, lda, at != 0, Bm, ldb, bt != 0, Cm, ldc, epi & 15);
   d.prec = (epi >> 4) & 15;  // 0 fp32, 1 bf16, 2 fp32-accurate bf16 split
-  d.variant = (epi >> 8) & 15;
-  if (d.variant == 9) { d.valu = 1; d.prec = GEMM_F32; d.variant = 0; }  // the fp32 VALU kernel
-  if ((epi >> 13) & 1) d.tm = 192;  // epi bit 13: the ring kernel's 192-row tiles where eligible
+  if (!force_desc((epi >> 8) & 15, &d)) return fail(nullptr, MVAE_EINVAL, "no such kernel number");
+  if ((epi >> 13) & 1) d.force.tile_m = 192;  // epi bit 13: the ring kernel's 192-row tiles where eligible
   d.x3 = (epi >> 16) & 3;           // epi bits 16-17: f32x ring plans on the plane-stacked kernels (x3 option)
   d.epi.act = act;
   d.epi.aux = aux;
@@ -310,7 +336,7 @@ extern "C" int mvae_bench_deint(int B, int D, int variant, int iters, void* stre
 
 // Time one GEMM shape of the step's kernel family (diagnostics): operands are allocated
 // and filled with uniform [-1,1) values inside, `iters` launches are timed with HIP events
-// on `stream` after 3 warm-ups. variant selects a kernel variant (0 = default).
+// on `stream` after 3 warm-ups. variant & 15: a kernel number (force_from_abi).
 extern "C" int mvae_bench_gemm(int M, int N, int K, int at, int bt, int batch, int variant, int iters,
                                void* stream, float* avg_ms) {
   if (M <= 0 || N <= 0 || K <= 0 || iters <= 0 || !avg_ms || batch <= 0) return MVAE_EINVAL;
@@ -328,12 +354,11 @@ extern "C" int mvae_bench_gemm(int M, int N, int K, int at, int bt, int batch, i
   const size_t na = sa * batch, nb = sb * batch, nc = (size_t)M * ldc * batch;
   GemmDesc d = gd(M, N, K, nullptr, lda, at != 0, nullptr, ldb, bt != 0, nullptr, ldc);
   d.batch = batch; d.sA = (long long)sa; d.sB = (long long)sb; d.sC = (long long)M * ldc;
-  d.variant = variant & 15;
   d.prec = (variant >> 4) & 15;  // 0 fp32, 1 bf16, 2 fp32-accurate bf16 split
-  if (d.variant == 9) { d.valu = 1; d.prec = GEMM_F32; d.variant = 0; }  // the fp32 VALU kernel
+  if (!force_desc(variant & 15, &d)) return fail(nullptr, MVAE_EINVAL, "mvae_bench_gemm: no such kernel number");
   d.diag = (variant >> 12) & 255; // kernel timing diagnostics (results meaningless; 32: A/B switch)
   // MVAE_BENCH_SPLIT (diagnostics): split-K forced (0 / unset: the planner's)
-  if (const char* sp = std::getenv("MVAE_BENCH_SPLIT"); sp && std::atoi(sp) > 0) d.split = std::atoi(sp);
+  if (const char* sp = std::getenv("MVAE_BENCH_SPLIT"); sp && std::atoi(sp) > 0) d.force.split = std::atoi(sp);
   // MVAE_BENCH_TILE_GROUP (diagnostics): the bf16 DMA kernels' tile order (m-tiles per band)
   if (const char* tg = std::getenv("MVAE_BENCH_TILE_GROUP"); tg && std::atoi(tg) >= 0) d.group = std::atoi(tg);
   const int np = d.prec == GEMM_F32 ? 0 : (d.prec == GEMM_BF16 ? 1 : 3);
@@ -703,7 +728,7 @@ extern "C" int mvae_debug_epi(const mvae_epi_args* args, void* stream) {
   if (a.M < 1 || a.N < 1 || a.K < 1) return bad("M, N and K must be at least 1");
   if (a.M > (1 << 24) || a.N > (1 << 24) || a.K > (1 << 24)) return bad("M, N or K too large");
   if (a.prec < GEMM_F32 || a.prec > GEMM_F32X) return bad("prec must be 0, 1 or 2");
-  {
+  {  // (argument validation: the subset of the kernel numbers this entry has always accepted)
     const int v = a.variant;
     if (v != 0 && v != 3 && v != 4 && !(v >= 10 && v <= 13)) return bad("variant must be 0, 3, 4, 10, 11, 12 or 13");
   }
@@ -749,7 +774,7 @@ extern "C" int mvae_debug_epi(const mvae_epi_args* args, void* stream) {
   Arena ar(st);
   GemmDesc d = gd(a.M, a.N, a.K, a.A, a.lda, false, a.B, a.ldb, a.bt != 0, a.du, a.ldc, a.epi);
   d.prec = a.prec;
-  d.variant = a.variant;
+  if (!force_from_abi(a.variant, &d.force)) return bad("no such kernel number");
   d.x3 = a.x3;
   GemmEpi& e = d.epi;
   e.act = a.act;
@@ -790,5 +815,48 @@ extern "C" int mvae_debug_epi(const mvae_epi_args* args, void* stream) {
     DIAG(gemm_run(d, ws, ws_n, st));
   }
   DIAG(hipStreamSynchronize(st));
+  return MVAE_OK;
+}
+
+// The plan gemm_run would launch for these arguments (include/mvae.h): host arithmetic only, no HIP
+// call, no pointer followed. The descriptor is built as mvae_debug_gemm / mvae_debug_epi build theirs.
+extern "C" int mvae_debug_plan(const mvae_plan_args* args, mvae_plan_out* out) {
+  const char* who = "mvae_debug_plan: ";
+  auto bad = [&](const std::string& m) { return fail(nullptr, MVAE_EINVAL, who + m); };
+  if (!args || !out) return bad("args or out is NULL");
+  const mvae_plan_args& a = *args;
+  if (a.M < 1 || a.N < 1 || a.K < 1 || a.batch < 1) return bad("M, N, K and batch must be at least 1");
+  if (a.prec < GEMM_F32 || a.prec > GEMM_F32X) return bad("prec must be 0, 1 or 2");
+  if (a.epi < EPI_STORE || a.epi > EPI_SIGMOID) return bad("epi must be in [0, 4]");
+  if (a.tm != 0 && a.tm != 192 && a.tm != 256) return bad("tm must be 0, 192 or 256");
+  if (a.x3 < 0 || a.x3 > 2) return bad("x3 must be in [0, 2]");
+  if (a.nA < 1 || a.nA > 3 || a.nB < 1 || a.nB > 3) return bad("nA and nB must be in [1, 3]");
+  if (a.split < 0) return bad("split must not be negative");
+  static const int flag = 0;  // (a set flag pointer: never read)
+  GemmDesc d = gd(a.M, a.N, a.K, nullptr, a.lda, a.at != 0, nullptr, a.ldb, a.bt != 0, (float*)a.C, a.ldc, a.epi);
+  d.batch = a.batch; d.sA = a.sA; d.sB = a.sB; d.sC = a.sC;
+  d.prec = a.prec;
+  d.Ap = (const unsigned short*)a.Ap; d.pA = a.pA; d.nA = a.nA;
+  d.Bp = (const unsigned short*)a.Bp; d.pB = a.pB; d.nB = a.nB;
+  if (a.dynA) d.dynA = &flag;
+  if (a.abits) d.Abits = reinterpret_cast<const unsigned*>(&flag);
+  d.x3 = a.x3;
+  GemmEpi& e = d.epi;
+  e.c32 = a.c32; e.padw = a.padw;
+  e.cp = (unsigned short*)a.cp; e.pc = a.pc; e.ncp = a.cp ? a.nA : 0;
+  e.aux = (const float*)a.aux; e.auxp = (const unsigned short*)a.auxp; e.ld_aux = a.ld_aux;
+  e.x = (const float*)a.x; e.xp = (const unsigned short*)a.xp; e.ldx = a.ldx;
+  if (a.xdyn) e.xdyn = &flag;
+  e.y = (float*)a.y; e.ldy = a.ldy;
+  if (!force_desc(a.variant, &d)) return bad("no such kernel number");
+  const bool valu_fits = gemm_valu_fits(d);  // (asked of the number alone, as the step's wiring asks)
+  if (a.valu) d.force.kernel = K_VALU;
+  d.force.tile_m = a.tm;
+  d.force.split = a.split;
+  const bool ws = a.ws && a.max_ws;
+  const GemmPlan pl = gemm_plan(d, ws ? (size_t)a.max_ws : 0, !misaligned(a.ws));
+  *out = mvae_plan_out{pl.kernel, pl.staging, pl.tm, pl.tn, pl.ntm, pl.ntn, pl.group, pl.split, pl.kchunk,
+                       (int)pl.lds_epilogue, (int)pl.vec_epilogue, pl.epi_launched, (int)valu_fits,
+                       (int)gemm_plan_refused(pl, ws, (size_t)a.max_ws), pl.ws_elems};
   return MVAE_OK;
 }

@@ -4,6 +4,7 @@
 #include <hip/hip_bf16.h>
 #include <cstddef>
 #include <cstdint>
+#include "gemm_plan.h"
 
 namespace mvae {
 
@@ -83,11 +84,8 @@ struct GemmDesc {
   const unsigned short* Bp = nullptr; long long pB = 0; int nB = 1;
   const int* dynA = nullptr;           // != 0 when A's residual planes may be nonzero
   int prec = GEMM_F32;                 // GemmPrec
-  int variant = 0;                     // kernel variant (diagnostics / A-B); 0 = default
-  int split = 0;                       // forced split-K (0 = planner)
+  GemmForce force;                     // what the caller fixes of the kernel choice (gemm_plan.h); default: nothing
   int diag = 0;                        // kernel timing diagnostics (gemm_bf16.hip PParams::diag)
-  int valu = 0;                        // 1: the fp32 VALU kernel (gemm_valu.hip; skinny shapes)
-  int tm = 0;                          // ring-kernel tile M forced (tests): 192 or 256; 0 = planner
   // diagnostics build of the twin kernel (mvae_bench_gemm, MVAE_STAMPS=1): per workgroup
   // s_memrealtime stamps {start, prologue copy landed, k-loop done, end} (never in the step)
   unsigned long long* stamps = nullptr;
@@ -122,30 +120,15 @@ inline size_t bitmat_words(int M, int K) { return (size_t)((M + 255) / 256) * bi
 hipError_t launch_bits_from_plane(const unsigned short* plane, int ld, bool trans, int M, int K,
                                   unsigned* out, int kts, int* nb, hipStream_t st);
 
-// Split-K choice for a GEMM (deterministic slab reduction when > 1).
-int gemm_plan_split(const GemmDesc& d, size_t max_ws);
-// Workspace elements (floats) the GEMM needs for its split-K slabs.
-size_t gemm_workspace_elems(const GemmDesc& d);
-// Launch. ws: device workspace of >= gemm_workspace_elems(d) floats.
+// Launch the plan gemm_plan(d, ws_elems) makes (gemm_plan.h; a split-K plan reduces its slabs in a
+// fixed order). ws: device workspace of >= gemm_workspace_elems(d) floats.
 hipError_t gemm_run(const GemmDesc& d, float* ws, size_t ws_elems, hipStream_t st);
+// the launchers gemm_run dispatches to by GemmPlan::kernel: p carries the plan's grid, tile and split
 namespace gemm { struct Params; }
-hipError_t gemm_bf16_launch(const gemm::Params& p, const GemmDesc& d, int epi, hipStream_t st);
-// bf16-plane GEMMs: the 256x256 wide kernel serves d? (shape/alignment), and its split-K plan
-bool gemm_bf16_wide(const GemmDesc& d);
-// fp32 VALU kernel for skinny products (an output dimension or K <= 64)
-bool gemm_valu_fits(const GemmDesc& d);
-int gemm_valu_split(const GemmDesc& d, size_t max_ws);
-hipError_t gemm_valu_launch(const gemm::Params& p, const GemmDesc& d, int epi, hipStream_t st);
-int gemm_bf16_wide_split(const GemmDesc& d, size_t max_ws);
-// tile N (256 or 128) of the wide kernel for d (the same plan as gemm_bf16_wide_split)
-int gemm_bf16_wide_tn(const GemmDesc& d, size_t max_ws);
-// ... and its tile M (256, or 192: k-contiguous A, not the BCE head)
-int gemm_bf16_wide_tm(const GemmDesc& d, size_t max_ws);
-// split-K, tile N and tile M of one plan (one planner pass per launch)
-void gemm_bf16_wide_plan(const GemmDesc& d, size_t max_ws, int* split, int* tn, int* tm);
+hipError_t gemm_bf16_launch(const gemm::Params& p, const GemmDesc& d, const GemmPlan& pl, hipStream_t st);
+hipError_t gemm_valu_launch(const gemm::Params& p, bool at, bool bt, int epi, hipStream_t st);
 // Number of column blocks the BCE epilogue writes per row (rowpart's inner dim).
 int gemm_bce_nblk(int N);
-constexpr int GEMM_TN_E8 = 2;  // gemm_bf16_wide_plan's tile N of the eight-phase kernel (gemm::TN_E8)
 
 // ---- the encoder's hidden layers in one launch (enc_chain.hip, bf16 planes) ----
 // layer: out = act(in W) on bf16 planes; W [K][ldw] (K incl. the bias row), N output columns,

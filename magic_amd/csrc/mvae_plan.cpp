@@ -110,7 +110,7 @@ void for_each_gemm(mvae_ctx* c, F fn) {
 
 bool in_xs(const mvae_ctx* c, const float* p) { return p >= c->xs && p < c->xs + (size_t)3 * c->B * c->ldx; }
 // a GEMM on the 256-row bf16-plane kernels
-bool plane_kernel(const GemmDesc& d) { return d.prec != GEMM_F32 && !d.valu && gemm_bf16_wide(d); }
+bool plane_kernel(const GemmDesc& d) { return gemm_wide_kernel(gemm_plan(d, ~size_t(0)).kernel); }
 
 int layout_params(mvae_ctx* c, const CreateOpts&) {
   const mvae_cfg* cfg = &c->cfg;
@@ -412,18 +412,20 @@ void wire(mvae_ctx* c, const CreateOpts& opt, GemmDesc& d) {
   const long long t256 = (long long)((d.M + 255) / 256) * ((d.N + 255) / 256) * d.batch;
   const bool wide_shape = d.M >= 256 && d.N >= 256 && !(d.K <= 64 && t256 < 256);
   // ... except the f32x latent head at small L over the tall stacked rows (C2: forward
-  // 12288 x 40 x 501, dgrad 16384 x 500 x 40): the ring kernel's plane products (variant 3, any
+  // 12288 x 40 x 501, dgrad 16384 x 500 x 40): the ring kernel's plane products (on any
   // shape) beat the VALU kernel there (24.3 / 23.9 us vs 30.8 / 38.0 us in the step,
   // profiles/r4/r4g_plan_c2.txt and bench_default_r4p_regions.txt), and its weight gradient
   // (501 x 40 x 8192, two products: 35.6 vs 40.7 us on the fp32 kernel, r4ar_thin_gemms.txt)
   const int lo = d.M < d.N ? d.M : d.N;
   const bool tall = d.M >= 4096 || (thin_ring == 2 && d.K >= 4096);
   if (gp == GEMM_F32X && e8_mode == 1 && !wide_shape && tall && lo >= 32 && d.K >= 32 &&
-      d.variant == 0 && thin_ring)
-    d.variant = 3;
+      !d.force.names_kernel() && thin_ring) {
+    d.force.kernel = K_RING;
+    d.force.any_shape = true;
+  }
   if (c->valu && gemm_valu_fits(d) && !(gp != GEMM_F32 && wide_shape)) {
     d.prec = GEMM_F32;
-    d.valu = 1;
+    d.force.kernel = K_VALU;
   }
   if (!c->np) return;
   const Planes a = planes_of(c, d.A), b = planes_of(c, d.B), o = planes_of(c, d.C);
@@ -434,13 +436,18 @@ void wire(mvae_ctx* c, const CreateOpts& opt, GemmDesc& d) {
   // exact split: GEMMs the 256x256 bf16 kernel does not serve (a dimension < 256: the
   // latent head, thin decoder layers) run faster as one native fp32 MFMA GEMM than as six
   // bf16 plane products on the 128x128 kernel; same accuracy class
-  if (gp == GEMM_F32X && !gemm_bf16_wide(d)) d.prec = GEMM_F32;
-  if (d.prec != GEMM_F32 && !d.valu && gemm_bf16_wide(d) && e8_mode != 1)
-    d.variant = e8_mode == 0 ? 15 : 13;
+  if (gp == GEMM_F32X && !plane_kernel(d)) d.prec = GEMM_F32;
+  // create option e8: 0 never the eight-phase kernel, 2 wherever its offsets fit (A/B, tests)
+  if (plane_kernel(d) && e8_mode == 0) {
+    d.force.no_e8 = true;
+  } else if (plane_kernel(d) && e8_mode != 1) {
+    d.force.kernel = K_E8;
+    d.force.any_shape = true;
+  }
   // bf16 mode: a plane-kernel DACT epilogue reads the activation's bf16 plane (act' from the
   // bf16-rounded output, the operand precision of this mode), so the forward epilogues write
   // the activations as planes only (no fp32 copy); dact_planes=0: the fp32 activations (A/B)
-  if (c->np == 1 && d.epi.mode == EPI_DACT && d.prec != GEMM_F32 && !d.valu && opt.dact_planes)
+  if (c->np == 1 && d.epi.mode == EPI_DACT && d.prec != GEMM_F32 && d.force.kernel != K_VALU && opt.dact_planes)
     d.epi.auxp = planes_of(c, d.epi.aux).p;
 }
 
@@ -547,12 +554,17 @@ int plan_pixel_bits(mvae_ctx* c, const CreateOpts& opt) {
 // the data-parallel parts)
 int plan_w0_chunks(mvae_ctx* c, const CreateOpts&) {
   const GemmDesc& w = c->bwd_enc[c->nenc];
-  const int w_split = gemm_plan_split(w, ~size_t(0));
-  int w_variant = w.variant;
-  if (plane_kernel(w) && w.variant == 0) {
-    int sp = 0, tn = 0, tm = 0;
-    gemm_bf16_wide_plan(w, ~size_t(0), &sp, &tn, &tm);
-    w_variant = tn == GEMM_TN_E8 ? 13 : (tn == 128 ? 11 : 12);  // (tm: 256 for an A^T operand)
+  const GemmPlan wp = gemm_plan(w, ~size_t(0));
+  GemmForce pin = w.force;
+  pin.split = wp.split;
+  if (gemm_wide_kernel(wp.kernel) && !w.force.names_kernel()) {
+    if (wp.kernel == K_E8) {
+      pin.kernel = K_E8;
+      pin.any_shape = true;
+    } else {  // (tile M: 256 for an A^T operand)
+      pin.kernel = K_RING;
+      pin.tile_n = wp.tn;
+    }
   }
   for (int R : {2, 4, 8}) {
     const int per = ((w.M + R - 1) / R + 255) / 256 * 256;
@@ -564,8 +576,7 @@ int plan_w0_chunks(mvae_ctx* c, const CreateOpts&) {
       if (d.Ap) d.Ap = w.Ap + m0;
       d.C = w.C + (size_t)m0 * w.ldc;  // output rows
       if (d.Abits) d.Abits = w.Abits + (size_t)(m0 / 256) * w.abits_kts * BITMAT_BLOCK_WORDS;
-      d.split = w_split;
-      d.variant = w_variant;
+      d.force = pin;
       c->w0c[R].push_back(d);
       c->w0m[R].push_back(m0);
     }
@@ -598,11 +609,9 @@ int plan_bce_split(mvae_ctx* c, const CreateOpts& opt) {
 int plan_xbw_split(mvae_ctx* c, const CreateOpts& opt) {
   if (opt.xbw_split != 2 || !c->bits_on) return MVAE_OK;
   const GemmDesc& f0 = c->fwd_enc[0];
-  int sp = 0, tn = 0, tm = 0;
-  gemm_bf16_wide_plan(f0, ~size_t(0), &sp, &tn, &tm);
-  const int tnc = tn == GEMM_TN_E8 ? 256 : tn;
-  const long long tiles = (long long)((f0.M + tm - 1) / tm) * ((f0.N + tnc - 1) / tnc) * f0.batch;
-  c->xbw_split = tiles * sp <= 224 ? 1 : 0;
+  // (bits_on: plan_pixel_bits found f0 on a 256-row kernel, so these are its 256- or 192-row tiles)
+  const GemmPlan fp = gemm_plan(f0, ~size_t(0));
+  c->xbw_split = (long long)fp.ntm * fp.ntn * f0.batch * fp.split <= 224 ? 1 : 0;
   return MVAE_OK;
 }
 
@@ -633,7 +642,7 @@ bool chain_of(const std::vector<const GemmDesc*>& ds, int rows, ChainArgs& ca) {
   bool ok = ca.nl >= 1 && ca.nl <= 4;
   for (int i = 0; i < ca.nl && i < 4; ++i) {
     const GemmDesc& d = *ds[i];
-    ok = ok && d.prec == GEMM_BF16 && !d.valu && d.epi.mode == EPI_ACT && d.epi.c32 == 0 &&
+    ok = ok && d.prec == GEMM_BF16 && d.force.kernel != K_VALU && d.epi.mode == EPI_ACT && d.epi.c32 == 0 &&
          d.epi.cp && d.epi.ncp == 1 && d.epi.padw == 2 && d.Ap && d.Bp && d.batch == 1 && !d.at &&
          !d.bt && d.K <= 512 && d.N <= 511 && d.M == ca.M && d.epi.act == ca.act;
     ChainLayer& cl = ca.l[i];
@@ -661,11 +670,12 @@ int log_plans(mvae_ctx* c, const CreateOpts& opt) {
   const size_t ws = c->ws_elems;
   for_each_gemm(c, [&](const GemmDesc& d, int r) {
     if (&d == &c->bwd_feat) return;  // (never listed; the log's text is kept as it is)
-    const int sp = gemm_plan_split(d, ws);
-    const bool wide = gemm_bf16_wide(d);
+    const GemmPlan pl = gemm_plan(d, ws);
+    // (the text as it always was: an eight-phase tile prints as 256x2)
+    const bool valu = pl.kernel == K_VALU, wide = gemm_wide_kernel(pl.kernel);
     std::fprintf(stderr, "[mvae plan] %-16s M %6d N %6d K %6d batch %d prec %d valu %d wide %d tile %dx%d split %d\n",
-                 r >= 0 ? c->region_names[r].c_str() : "?", d.M, d.N, d.K, d.batch, d.prec, d.valu,
-                 (int)wide, wide ? gemm_bf16_wide_tm(d, ws) : 0, wide ? gemm_bf16_wide_tn(d, ws) : 0, sp);
+                 r >= 0 ? c->region_names[r].c_str() : "?", d.M, d.N, d.K, d.batch, d.prec, (int)valu,
+                 (int)wide, wide ? pl.tm : 0, wide ? (pl.kernel == K_E8 ? 2 : pl.tn) : 0, pl.split);
     if (&d == &c->fwd_enc.back() && c->chain)
       std::fprintf(stderr, "[mvae plan] enc_fwd_chain    layers 1..%d in one launch, %d rows per workgroup\n",
                    c->nenc - 1, enc_chain_rows(c->chain_args.M, c->chain_args.rows));
@@ -717,7 +727,9 @@ void mvae::bce_split_descs(const GemmDesc& f, int c0, GemmDesc* pa, GemmDesc* pb
   if (b.epi.y) b.epi.y = f.epi.y + c0;
   b.epi.rp_ld = rp_ld;
   b.epi.rp_off = f.epi.rp_off + c0 / 128;
-  b.variant = 11;  // the ring kernel at 256x128 tiles
+  b.force = GemmForce{};  // the ring kernel at 256x128 tiles, whatever f forces
+  b.force.kernel = K_RING;
+  b.force.tile_n = 128;
   *pa = a;
   *pb = b;
 }

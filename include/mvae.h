@@ -445,6 +445,52 @@ int mvae_overlap_pairs(const unsigned char* locks, const unsigned char* keys, in
                        const float* coef, int n_rot, int* area_out, int* pose_out,
                        void* work, void* stream);
 
+/* ---- verified retrieval: a shortlist ordered by exact overlap, a key shown at its pose ---------
+ * Additive to ABI 7. Context-free, allocate nothing, enqueue on `stream`, like mvae_overlap_pairs;
+ * Lb, Kr_r, area and pose are those of the definition above, bit for bit.
+ *
+ * mvae_rerank: lock i of the call is lock lock_idx[i] (device int32 [N], NULL: i); cand: device int32
+ * [N][R], the key index of each entry of its shortlist, a negative value being an empty entry, as
+ * mvae_match_ex leaves them (it indexes no table and costs next to nothing). Pair (i, c) is that lock
+ * with key cand[i][c]. Each row is then ordered by exact area: entry e gets rank = the number of
+ * entries e' of the row with area' > area, or area' == area and column e' < e -- larger area first,
+ * ties in cand's column order (the model's), empties (area -1) last in their column order; a key
+ * listed twice in a row stays twice. Outputs, device int32, every slot written:
+ *   key_out  [N][R]     the key at each rank, -1 for empties
+ *   area_out [N][R]     its area, -1 for empties
+ *   pose_out [N][R][3]  or NULL: its pose (r, dy, dx); 0, 0, 0 for empties
+ *   from_out [N][R]     or NULL: the column of cand the entry came from
+ * work: device buffer of mvae_rerank_work_bytes(...) bytes, 8-byte aligned (the overlap partials of
+ * the N R pairs, the two expanded index lists, the unordered areas and poses): its contents need not
+ * survive the call. The ranges of lock_idx and of the non-negative entries of cand are the caller's
+ * precondition, not checked, as for mvae_overlap_pairs.
+ * MVAE_EINVAL with a message (mvae_last_error(NULL)) beginning "mvae_rerank", before any launch: a null
+ * table, cand, coef, key_out or area_out, N outside 1 .. 2^31 - 1, R outside 1 .. 64, n_rot outside
+ * 1 .. 2^24, height or width outside 1 .. 256, a misaligned coef or work, a null work.
+ * mvae_rerank_work_bytes returns 0 for arguments mvae_rerank refuses.
+ *
+ * mvae_overlap_place: for pair i < count of lock lock_idx[i] and key key_idx[i] (NULL: i, as for
+ * mvae_overlap_pairs; not checked) and pose[i] = (r, dy, dx), device int32 [count][3]:
+ *   P[y, x]     = Kr_r[y - dy, x - dx] inside the image, 0 outside
+ *   overlay_out   device uint8 [count][H][W] or NULL: byte = (Lb ? 1 : 0) | (P ? 2 : 0)
+ *   stats_out     device int32 [count][4] or NULL: (|Lb|, |Kr_r|, |P|, |Lb & P|); for a pose of
+ *                 mvae_overlap_pairs or mvae_rerank the last is that call's area
+ * A pose out of range (r outside [0, n_rot), |dy| >= H or |dx| >= W) is defined: no coef entry and
+ * no key pixel is read, the overlay is the lock alone and the stats are (|Lb|, -1, -1, -1).
+ * MVAE_EINVAL with a message beginning "mvae_overlap_place", before any launch: a null table, coef or
+ * pose, both outputs null, count < 1, n_rot outside 1 .. 2^24, height or width outside 1 .. 256, a
+ * misaligned coef. */
+size_t mvae_rerank_work_bytes(int64_t N, int R, int n_rot, int height, int width);
+int mvae_rerank(const unsigned char* locks, const unsigned char* keys, int height, int width,
+                const int* lock_idx, const int* cand, int64_t N, int R,
+                const float* coef, int n_rot,
+                int* key_out, int* area_out, int* pose_out, int* from_out,
+                void* work, void* stream);
+int mvae_overlap_place(const unsigned char* locks, const unsigned char* keys, int height, int width,
+                       const int* lock_idx, const int* key_idx, int64_t count,
+                       const float* coef, int n_rot, const int* pose,
+                       unsigned char* overlay_out, int* stats_out, void* stream);
+
 /* ---- diagnostics ------------------------------------------------------------------ */
 /* HIP-event timing of named regions (one GEMM incl. its split-K reduction, or one
  * bandwidth kernel group), recorded on the launch stream while enabled.               */

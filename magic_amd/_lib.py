@@ -196,6 +196,12 @@ _SIGS = {
     "mvae_overlap_work_bytes": ([C.c_int64, C.c_int, C.c_int, C.c_int], C.c_size_t),
     "mvae_overlap_pairs": ([C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64,
                             C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+    "mvae_rerank_work_bytes": ([C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int], C.c_size_t),
+    "mvae_rerank": ([C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
+                     C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+                    C.c_int),
+    "mvae_overlap_place": ([C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64,
+                            C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
     "mvae_timing_enable": ([C.c_void_p, C.c_int], C.c_int),
     "mvae_timing_select": ([C.c_void_p, C.c_int], C.c_int),
     "mvae_timing_marker": ([C.c_void_p, C.c_int, C.c_int], C.c_int),

@@ -297,6 +297,24 @@ size_t overlap_work_bytes(long long count, int n_rot);
 hipError_t launch_overlap_pairs(const unsigned char* locks, const unsigned char* keys, int H, int W,
                                 const int* lock_idx, const int* key_idx, long long count, const float* coef,
                                 int n_rot, int* area_out, int* pose_out, void* work, hipStream_t st);
+// ---- verified retrieval: a shortlist ordered by exact overlap, a key placed at its pose (rerank.hip) ----
+// Pair (i, c), c < R <= 64: lock lock_idx[i] (null: i) and key cand[i][c] (negative: an empty entry,
+// which indexes no table); area and pose as launch_overlap_pairs, each row then ordered by area
+// (larger first, ties in column order, empties last with key -1, area -1, pose 0): key_out, area_out,
+// pose_out (or null), from_out (or null: the column an entry came from), all [N][R]. work of
+// rerank_work_bytes bytes, 8-byte aligned. N in 1 .. RERANK_MAX_LOCKS (hipErrorInvalidValue otherwise).
+constexpr long long RERANK_MAX_LOCKS = 0x7fffffffll;
+size_t rerank_work_bytes(long long N, int R, int n_rot);
+hipError_t launch_rerank(const unsigned char* locks, const unsigned char* keys, int H, int W, const int* lock_idx,
+                         const int* cand, long long N, int R, const float* coef, int n_rot, int* key_out,
+                         int* area_out, int* pose_out, int* from_out, void* work, hipStream_t st);
+// overlay_out[i] (or null) = lock bit | 2 * bit of the key rotated by coef[r] and shifted by (dy, dx),
+// (r, dy, dx) = pose[i]; stats_out[i] (or null) = (|Lb|, |Kr_r|, |P|, |Lb & P|). A pose out of range
+// reads no coef entry and no key pixel: the lock alone and (|Lb|, -1, -1, -1).
+hipError_t launch_overlap_place(const unsigned char* locks, const unsigned char* keys, int H, int W,
+                                const int* lock_idx, const int* key_idx, long long count, const float* coef,
+                                int n_rot, const int* pose, unsigned char* overlay_out, int* stats_out,
+                                hipStream_t st);
 // ---- conv-encoder tower (conv_tower.hip, conv_mfma.hip) ----
 // NHWC fp32 activations of the stacked batch (3B forward rows, 4B backward rows); S = image
 // side, S1 = S/2 (after pool 1), S2 = S/4 (after pool 2).

@@ -1,5 +1,5 @@
 // libmvae: retrieval (match*, pair_scores, match_merge) and the context-free batch and overlap
-// helpers (make_batch*, overlap_*).
+// helpers (make_batch*, overlap_*, rerank*).
 #include "mvae_ctx.h"
 
 // the match workspace holds at least `need` bytes (growing it waits for the whole device first)
@@ -233,5 +233,53 @@ extern "C" int mvae_overlap_pairs(const unsigned char* locks, const unsigned cha
     return fail(nullptr, MVAE_EINVAL, "mvae_overlap_pairs: work must be 8-byte aligned");
   MV_TRY(nullptr, "", launch_overlap_pairs(locks, keys, height, width, lock_idx, key_idx, count, coef, n_rot, area_out,
                                            pose_out, work, (hipStream_t)stream));
+  return MVAE_OK;
+}
+
+extern "C" size_t mvae_rerank_work_bytes(int64_t N, int R, int n_rot, int height, int width) {
+  if (N < 1 || N > RERANK_MAX_LOCKS || R < 1 || R > 64 || n_rot < 1 || n_rot > OVERLAP_MAX_ROT || height < 1 ||
+      height > 256 || width < 1 || width > 256)
+    return 0;  // mvae_rerank refuses these arguments
+  return rerank_work_bytes(N, R, n_rot);
+}
+
+extern "C" int mvae_rerank(const unsigned char* locks, const unsigned char* keys, int height, int width,
+                           const int* lock_idx, const int* cand, int64_t N, int R, const float* coef, int n_rot,
+                           int* key_out, int* area_out, int* pose_out, int* from_out, void* work, void* stream) {
+  if (!locks || !keys || !cand || !coef || !key_out || !area_out)
+    return fail(nullptr, MVAE_EINVAL, "mvae_rerank: null locks, keys, cand, coef, key_out or area_out");
+  if (N < 1 || N > RERANK_MAX_LOCKS) return fail(nullptr, MVAE_EINVAL, "mvae_rerank: N must be in [1, 2^31 - 1]");
+  if (R < 1 || R > 64) return fail(nullptr, MVAE_EINVAL, "mvae_rerank: R must be in [1, 64]");
+  if (n_rot < 1 || n_rot > OVERLAP_MAX_ROT)
+    return fail(nullptr, MVAE_EINVAL, "mvae_rerank: n_rot must be in [1, 16777216]");
+  if (height < 1 || height > 256 || width < 1 || width > 256)
+    return fail(nullptr, MVAE_EINVAL, "mvae_rerank: height and width must be in [1, 256]");
+  if ((reinterpret_cast<uintptr_t>(coef) & 15) != 0)
+    return fail(nullptr, MVAE_EINVAL, "mvae_rerank: coef must be 16-byte aligned");
+  if (!work) return fail(nullptr, MVAE_EINVAL, "mvae_rerank: work is null but mvae_rerank_work_bytes is not 0");
+  if ((reinterpret_cast<uintptr_t>(work) & 7) != 0)
+    return fail(nullptr, MVAE_EINVAL, "mvae_rerank: work must be 8-byte aligned");
+  MV_TRY(nullptr, "", launch_rerank(locks, keys, height, width, lock_idx, cand, N, R, coef, n_rot, key_out, area_out,
+                                    pose_out, from_out, work, (hipStream_t)stream));
+  return MVAE_OK;
+}
+
+extern "C" int mvae_overlap_place(const unsigned char* locks, const unsigned char* keys, int height, int width,
+                                  const int* lock_idx, const int* key_idx, int64_t count, const float* coef,
+                                  int n_rot, const int* pose, unsigned char* overlay_out, int* stats_out,
+                                  void* stream) {
+  if (!locks || !keys || !coef || !pose)
+    return fail(nullptr, MVAE_EINVAL, "mvae_overlap_place: null locks, keys, coef or pose");
+  if (!overlay_out && !stats_out)
+    return fail(nullptr, MVAE_EINVAL, "mvae_overlap_place: overlay_out and stats_out are both null");
+  if (count < 1) return fail(nullptr, MVAE_EINVAL, "mvae_overlap_place: count must be at least 1");
+  if (n_rot < 1 || n_rot > OVERLAP_MAX_ROT)
+    return fail(nullptr, MVAE_EINVAL, "mvae_overlap_place: n_rot must be in [1, 16777216]");
+  if (height < 1 || height > 256 || width < 1 || width > 256)
+    return fail(nullptr, MVAE_EINVAL, "mvae_overlap_place: height and width must be in [1, 256]");
+  if ((reinterpret_cast<uintptr_t>(coef) & 15) != 0)
+    return fail(nullptr, MVAE_EINVAL, "mvae_overlap_place: coef must be 16-byte aligned");
+  MV_TRY(nullptr, "", launch_overlap_place(locks, keys, height, width, lock_idx, key_idx, count, coef, n_rot, pose,
+                                           overlay_out, stats_out, (hipStream_t)stream));
   return MVAE_OK;
 }

@@ -86,6 +86,12 @@ __global__ __launch_bounds__(OV_T) void overlap_kernel(
   const int WS = 2 * nseg;         // words per packed row
   const int KS = WS + 2;           // row stride of Kp
   const size_t HW = (size_t)H * W;
+  // an empty shortlist entry (mvae_rerank: a negative key index) indexes no table: a zero partial,
+  // before the first barrier and for the whole workgroup alike
+  if (key_idx && key_idx[pair] < 0) {
+    if (tid == 0) work[(size_t)pair * nchunks + chunk] = 0ull;
+    return;
+  }
   const unsigned char* L = locks + (size_t)(lock_idx ? lock_idx[pair] : pair) * HW;
   const unsigned char* K = keys + (size_t)(key_idx ? key_idx[pair] : pair) * HW;
 

@@ -101,11 +101,15 @@ def train(vae, batches, n_samples: int, training_epochs: int = 60, driver: str =
     return vae, history
 
 
-def retrieve_report(vae, batches, k: int, log=print, shard=None, ranks: bool = False):
+def retrieve_report(vae, batches, k: int, log=print, shard=None, ranks: bool = False, rerank=None,
+                    rerank_angles=360):
     """The ``--retrieve K`` report over the stream's lock / key tables; returns the ``Retrieval``.
-    ``shard`` / ``ranks``: ``--retrieve-shard S`` / ``--retrieve-ranks``."""
+    ``shard`` / ``ranks``: ``--retrieve-shard S`` / ``--retrieve-ranks``; ``rerank`` / ``rerank_angles``:
+    ``--retrieve-rerank R`` / ``--rerank-angles A``."""
     from . import retrieval
-    r = retrieval.retrieve(vae, batches.locks, batches.keys, k, normalize=batches.normalize, shard=shard, ranks=ranks)
+    more = {} if rerank is None else dict(rerank=rerank, rerank_angles=rerank_angles)
+    r = retrieval.retrieve(vae, batches.locks, batches.keys, k, normalize=batches.normalize, shard=shard, ranks=ranks,
+                           **more)
     log(retrieval.report(r))
     return r
 
@@ -133,6 +137,11 @@ def main(argv=None):
                          "(a gallery larger than the device)")
     ap.add_argument("--retrieve-ranks", action="store_true",
                     help="with --retrieve: also the rank of key i for lock i -- MRR and median rank")
+    ap.add_argument("--retrieve-rerank", type=int, default=0, metavar="R",
+                    help="with --retrieve: take the model's R best keys of every lock (K <= R <= 64), compute "
+                         "their exact overlap on the GPU and report the K best by exact area")
+    ap.add_argument("--rerank-angles", type=int, default=360, metavar="A",
+                    help="with --retrieve-rerank: the key is tried at A equally spaced rotations")
     ap.add_argument("--labels", choices=("sampled", "computed"), default="sampled",
                     help="sampled: the source's areas, or for synthetic shapes draws from the reference's "
                          "recorded areas (unrelated to the images); computed: the maximum overlap of each "
@@ -156,6 +165,10 @@ def main(argv=None):
         ap.error(f"--pairs {args.pairs} needs --labels computed")
     if not 0.0 <= args.cross <= 1.0 or args.mine_k < 1 or args.mine_every < 1:
         ap.error("--cross must be in [0, 1], --mine-k and --mine-every at least 1")
+    if (args.retrieve_rerank or args.rerank_angles != 360) and args.retrieve <= 0:
+        ap.error("--retrieve-rerank and --rerank-angles need --retrieve")
+    if args.retrieve_rerank < 0 or args.rerank_angles < 1:
+        ap.error("--retrieve-rerank must be positive and --rerank-angles at least 1")
     cfg = preset(args.preset, image_size=args.image_size, batch=args.batch or None)
     eight_c = args.preset in ("8c", "8d", "8e", "8f")
     driver = args.driver or ("8c" if eight_c else "11a")
@@ -173,7 +186,8 @@ def main(argv=None):
     train(vae, batches, max(args.samples_per_epoch, cfg.batch), args.epochs, driver=driver, on_epoch=on_epoch)
     print(f"done in {time.time() - t0:.1f}s", file=sys.stderr)
     if args.retrieve > 0:
-        retrieve_report(vae, batches, args.retrieve, shard=args.retrieve_shard or None, ranks=args.retrieve_ranks)
+        retrieve_report(vae, batches, args.retrieve, shard=args.retrieve_shard or None, ranks=args.retrieve_ranks,
+                        rerank=args.retrieve_rerank or None, rerank_angles=args.rerank_angles)
     vae.close()
 
 

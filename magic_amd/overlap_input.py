@@ -130,6 +130,89 @@ def max_overlap(locks: torch.Tensor, keys: torch.Tensor, lock_idx: Optional[torc
     return areas, pose
 
 
+def _check_tables(what: str, locks, keys):
+    for t in (locks, keys):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.uint8 or not t.is_contiguous() \
+                or t.dim() != 3:
+            raise ValueError(f"{what}: contiguous uint8 device tables [n, H, W] expected")
+    if keys.shape[1:] != locks.shape[1:] or keys.device != locks.device:
+        raise ValueError(f"{what}: the tables must share H, W and the device")
+
+
+def _is_list(t, dim: int) -> bool:
+    return isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() \
+        and t.dim() == dim
+
+
+def rerank(locks: torch.Tensor, keys: torch.Tensor, cand: torch.Tensor, lock_idx: Optional[torch.Tensor] = None,
+           angles=360) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """A shortlist verified (``mvae_rerank``): ``cand`` int32 device ``[N, R]``, R <= 64, holds for lock
+    ``lock_idx[i]`` (``None``: ``i``) the keys a model proposes, best first; a negative entry is empty.
+    Every listed pair gets its exact ``max_overlap`` over ``angles`` and each row is ordered by that area
+    (larger first, ties in ``cand``'s order, empties last). uint8 device tables as for ``max_overlap``.
+    Returns int32 device tensors ``(keys [N, R], areas [N, R], poses [N, R, 3], src [N, R])``: -1, -1 and
+    (0, 0, 0) for empties; ``src`` is the column of ``cand`` an entry came from."""
+    from . import _lib
+    lib = _lib.load()
+    _check_tables("rerank", locks, keys)
+    if not _is_list(cand, 2) or cand.shape[0] < 1 or not 1 <= cand.shape[1] <= 64:
+        raise ValueError("rerank: cand must be an int32 device tensor [N, R] with N >= 1 and 1 <= R <= 64")
+    if lock_idx is not None and (not _is_list(lock_idx, 1) or lock_idx.shape[0] != cand.shape[0]):
+        raise ValueError("rerank: lock_idx must be an int32 device list [N]")
+    N, R = int(cand.shape[0]), int(cand.shape[1])
+    if lock_idx is None and N > locks.shape[0]:
+        raise ValueError("rerank: more rows than locks in the table without an index list")
+    h, w = int(locks.shape[1]), int(locks.shape[2])
+    dev = locks.device
+    coef = torch.from_numpy(angle_coefficients(angles, h, w)).to(dev)
+    n_rot = coef.shape[0]
+    new = lambda *s: torch.empty(*s, dtype=torch.int32, device=dev)  # noqa: E731
+    key_o, area_o, pose_o, src_o = new(N, R), new(N, R), new(N, R, 3), new(N, R)
+    nbytes = lib.mvae_rerank_work_bytes(N, R, n_rot, h, w)
+    work = torch.empty(max(nbytes // 8, 1), dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.mvae_rerank(locks.data_ptr(), keys.data_ptr(), h, w,
+                             lock_idx.data_ptr() if lock_idx is not None else None, cand.data_ptr(), N, R,
+                             coef.data_ptr(), n_rot, key_o.data_ptr(), area_o.data_ptr(), pose_o.data_ptr(),
+                             src_o.data_ptr(), work.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(lib, None, rc)
+    return key_o, area_o, pose_o, src_o
+
+
+def place(locks: torch.Tensor, keys: torch.Tensor, lock_idx: Optional[torch.Tensor],
+          key_idx: Optional[torch.Tensor], pose: torch.Tensor, angles=360) -> Tuple[torch.Tensor, torch.Tensor]:
+    """A key shown at a pose (``mvae_overlap_place``): for pair ``i`` of lock ``lock_idx[i]`` and key
+    ``key_idx[i]`` (``None``: ``i``) and ``pose[i] = (angle index, dy, dx)`` (int32 device ``[count, 3]``, as
+    ``max_overlap`` / ``rerank`` return them, over the same ``angles``) -> ``(overlay uint8 [count, H, W],
+    stats int32 [count, 4])``: overlay bit 0 is the lock's foreground, bit 1 the key's after the rotation
+    and the shift; stats = (lock pixels, rotated key pixels, of those inside the image after the shift,
+    shared pixels = the area). A pose out of range shows the lock alone with stats (lock pixels, -1, -1,
+    -1)."""
+    from . import _lib
+    lib = _lib.load()
+    _check_tables("place", locks, keys)
+    if not _is_list(pose, 2) or pose.shape[0] < 1 or pose.shape[1] != 3:
+        raise ValueError("place: pose must be an int32 device tensor [count, 3] with count >= 1")
+    count = int(pose.shape[0])
+    for t, table in ((lock_idx, locks), (key_idx, keys)):
+        if t is not None and (not _is_list(t, 1) or t.shape[0] != count):
+            raise ValueError("place: int32 device index lists [count] expected")
+        if t is None and count > table.shape[0]:
+            raise ValueError("place: more pairs than images in the table without an index list")
+    h, w = int(locks.shape[1]), int(locks.shape[2])
+    dev = locks.device
+    coef = torch.from_numpy(angle_coefficients(angles, h, w)).to(dev)
+    overlay = torch.empty(count, h, w, dtype=torch.uint8, device=dev)
+    stats = torch.empty(count, 4, dtype=torch.int32, device=dev)
+    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    with torch.cuda.device(dev):
+        rc = lib.mvae_overlap_place(locks.data_ptr(), keys.data_ptr(), h, w, ptr(lock_idx), ptr(key_idx), count,
+                                    coef.data_ptr(), coef.shape[0], pose.data_ptr(), overlay.data_ptr(),
+                                    stats.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(lib, None, rc)
+    return overlay, stats
+
+
 class PairBatch:
     """One batch described by its sources instead of materialised: the uint8 device tables
     ``locks`` / ``keys`` [n, H, W], the example ``idx`` int32 [B] of each row and its rotation

@@ -25,6 +25,12 @@ class Retrieval(NamedTuple):
     median_rank: Optional[float] = None  # median of ranks + 1
     true_hit_at_1: Optional[float] = None  # share of locks whose truly best key (``truth``) comes first
     true_hit_at_k: Optional[float] = None  # ... or is among the k returned
+    # filled only by ``retrieve(rerank=R)``: the list above is then the k best of the model's R by exact area
+    areas: Optional[np.ndarray] = None      # [n_locks, k] exact overlap area of each returned key
+    poses: Optional[np.ndarray] = None      # [n_locks, k, 3] its pose (angle index, dy, dx)
+    shortlist: Optional[np.ndarray] = None  # [n_locks, R] the model's list before verification
+    moved: Optional[float] = None           # share of locks whose first key changed
+    area_regret: Optional[float] = None     # with ``truth``: mean of truth[i].max() - truth[i, indices[i, 0]]
 
 
 def _sharded(vae, locks, keys, k, order, normalize, return_dist, shard, ranks):
@@ -91,7 +97,8 @@ def overlap_matrix(locks, keys, angles=360, chunk: int = 1 << 16) -> np.ndarray:
 
 
 def retrieve(vae, locks, keys, k: int = 10, order: int = 1, normalize: bool = True,
-             return_dist: bool = False, shard: Optional[int] = None, ranks: bool = False, truth=None):
+             return_dist: bool = False, shard: Optional[int] = None, ranks: bool = False, truth=None,
+             rerank: Optional[int] = None, rerank_angles=360):
     """``locks``, ``keys``: uint8 tables ``[n, S, S]`` and ``[m, S, S]`` (arrays or device tensors).
     Returns a ``Retrieval`` (and the ``[n, m]`` score matrix when ``return_dist``). The distance is
     trained to equal the overlap area, so the default ``order`` +1 ranks the largest predicted
@@ -106,7 +113,20 @@ def retrieve(vae, locks, keys, k: int = 10, order: int = 1, normalize: bool = Tr
     with ``mrr`` and ``median_rank`` (1-based) of them. ``truth``: an ``[n, m]`` matrix of true labels
     (``overlap_matrix``); ``true_hit_at_1`` / ``true_hit_at_k`` are then the share of locks whose
     truly best key (the largest entry of its row, the smallest index on ties) is the first / among the
-    ``k`` returned."""
+    ``k`` returned.
+
+    ``rerank=R`` (k <= R <= min(m, 64)): retrieve, then verify. The model's ``R`` best keys of every lock
+    (the same one-shot or sharded path with ``k`` replaced by ``R``) are the shortlist; the exact overlap
+    and pose of those n R pairs over ``rerank_angles`` are computed on the device
+    (``overlap_input.rerank``; both tables go there whole, as for ``overlap_matrix``), each list is
+    ordered by exact area (ties keep the model's order) and ``indices`` / ``values`` are its ``k`` best
+    with each key's model score. Every hit rate is then judged on that verified list, and ``areas``,
+    ``poses``, ``shortlist``, ``moved`` and (with ``truth``) ``area_regret`` are filled."""
+    if rerank is not None:
+        if not (1 <= k <= rerank <= min(len(keys), 64)):
+            raise ValueError(f"retrieve: rerank must satisfy k <= rerank <= min(m, 64) (k = {k}, rerank = {rerank}, "
+                             f"m = {len(keys)})")
+    k_out, k = k, (k if rerank is None else int(rerank))
     if truth is not None:
         truth = truth.cpu().numpy() if isinstance(truth, torch.Tensor) else np.asarray(truth)
         if truth.shape != (len(locks), len(keys)):
@@ -116,6 +136,9 @@ def retrieve(vae, locks, keys, k: int = 10, order: int = 1, normalize: bool = Tr
     else:
         out = _one_shot(vae, locks, keys, k, order, normalize, return_dist)
     val, ind = out[0], out[1]
+    verified = (None,) * 5
+    if rerank is not None:
+        val, ind, verified = _verify(locks, keys, val, ind, k_out, rerank_angles, truth)
     k = val.shape[1]
     n = min(len(val), len(keys))
     own = np.arange(n)[:, None]
@@ -128,8 +151,43 @@ def retrieve(vae, locks, keys, k: int = 10, order: int = 1, normalize: bool = Tr
     if truth is not None:
         best = np.argmax(truth, axis=1)[:, None]  # the first maximum of a row
         extra += (float((ind[:, :1] == best).any(1).mean()), float((ind == best).any(1).mean()))
-    res = Retrieval(val, ind, hit1, hitk, k, order, *extra)
+    else:
+        extra += (None, None)
+    res = Retrieval(val, ind, hit1, hitk, k, order, *extra, *verified)
     return (res, out[2]) if return_dist else res
+
+
+def _verify(locks, keys, val, ind, k, angles, truth):
+    """The model's lists ``val`` / ``ind`` [n, R] -> the k best of each by exact area, with the model's
+    score of each key, and the ``Retrieval`` fields of the verified list."""
+    from .overlap_input import rerank
+    dev = locks.device if isinstance(locks, torch.Tensor) and locks.is_cuda else torch.device("cuda")
+    up = lambda t: torch.as_tensor(t).to(dev).contiguous()  # noqa: E731
+    cand = torch.from_numpy(np.ascontiguousarray(ind, dtype=np.int32)).to(dev)
+    key, area, pose, src = (t.cpu().numpy() for t in rerank(up(locks), up(keys), cand, angles=angles))
+    score = np.take_along_axis(val, src.astype(np.int64), axis=1)
+    moved = float((key[:, 0] != ind[:, 0]).mean())
+    regret = None
+    if truth is not None:
+        regret = float((truth.max(1) - truth[np.arange(len(truth)), key[:, 0]]).mean())
+    return score[:, :k], key[:, :k], (area[:, :k], pose[:, :k], np.asarray(ind), moved, regret)
+
+
+def placed(r: Retrieval, locks, keys, rank: int = 0, angles=360):
+    """Each lock with its ``rank``-th verified key at that key's pose: ``(overlay uint8 [n, H, W], stats
+    int32 [n, 4])`` device tensors of ``overlap_input.place``; ``stats[:, 3]`` is ``r.areas[:, rank]``.
+    ``r`` comes from ``retrieve(..., rerank=R, rerank_angles=angles)`` over the same tables."""
+    from .overlap_input import place
+    if r.areas is None:
+        raise ValueError("placed: the Retrieval holds no poses; call retrieve(..., rerank=R)")
+    if not 0 <= rank < r.indices.shape[1]:
+        raise ValueError(f"placed: rank must be in [0, {r.indices.shape[1]})")
+    dev = locks.device if isinstance(locks, torch.Tensor) and locks.is_cuda else torch.device("cuda")
+    up = lambda t: torch.as_tensor(t).to(dev).contiguous()  # noqa: E731
+    n = len(r.indices)
+    dn = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)  # noqa: E731
+    return place(up(locks), up(keys), torch.arange(n, dtype=torch.int32, device=dev), dn(r.indices[:, rank]),
+                 dn(r.poses[:, rank]), angles=angles)
 
 
 def _one_shot(vae, locks, keys, k, order, normalize, return_dist):
@@ -146,4 +204,9 @@ def report(r: Retrieval) -> str:
         s += f", MRR = {r.mrr:.4f}, median rank = {r.median_rank:g} over {len(r.ranks)} locks"
     if r.true_hit_at_1 is not None:
         s += f"; truly best key: hit@1 = {r.true_hit_at_1:.4f}, hit@{r.k} = {r.true_hit_at_k:.4f}"
+    if r.areas is not None:
+        s += (f"; verified: the hit rates are of the model's {r.shortlist.shape[1]} best ordered by exact overlap, "
+              f"first key moved for {r.moved:.4f} of the locks, mean area of the first key = {r.areas[:, 0].mean():.1f}")
+        if r.area_regret is not None:
+            s += f", area regret = {r.area_regret:.2f}"
     return s

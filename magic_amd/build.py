@@ -22,9 +22,9 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("MVAE_ARCH", "gfx950")
 SOURCES = ["mvae_api.cpp", "mvae_plan.cpp", "mvae_step.cpp", "mvae_match.cpp", "mvae_diag.cpp",
            "gemm_plan.cpp", "gemm_f32.hip", "gemm_bf16.hip", "gemm_bf16e.hip", "gemm_valu.hip", "mvae_kernels.hip",
-           "conv_tower.hip", "conv_mfma.hip", "enc_chain.hip", "pairs_bits.hip", "images_bits.hip", "match.hip",
+           "batch_input.hip", "conv_tower.hip", "conv_mfma.hip", "enc_chain.hip", "match.hip",
            "overlap.hip", "rerank.hip"]
-HEADERS = ["mvae_ctx.h", "mvae_internal.h", "gemm_plan.h", "gemm_common.h", "deint_bits.h",
+HEADERS = ["mvae_ctx.h", "mvae_internal.h", "gemm_plan.h", "gemm_common.h",
            os.path.join("..", "..", "include", "mvae.h")]
 CFLAGS = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-Wno-unused-result",
           "-Wno-unused-value", "-I", os.path.join(ROOT, "include")]

@@ -38,8 +38,8 @@ constexpr uint64_t EVAL_STREAM = 1ull << 63;
 struct mvae_ctx {
   mvae_cfg cfg{};
   int device = 0;
-  // a batch given as (tables, idx, coefficients) (the *_pairs entry points) where the direct
-  // kernel does not apply: X materialised here (launch_make_batch), allocated on first need
+  // a batch given as (tables, idx, coefficients) (the *_pairs entry points) or an embedding pass
+  // where the direct kernel does not apply: X materialised here, allocated on first need
   float* pairs_x = nullptr;
   // mvae_match's workspace, allocated at the first call that needs it and grown on demand: the
   // per-split top-k lists [N][splits][k] (values, indices) and, for the cosine metric, the column
@@ -121,16 +121,15 @@ struct mvae_ctx {
   int* dyn = nullptr;    // bf16/f32x: some de-interleaved pixel not exact in bf16?
   int* dyn_cur = nullptr;  // ... its slot of the last de-interleave (two slots, used in turn)
   int x32mask = 7;       // fp32 row blocks of xs the step reads (bit c: 0 rot, 1 lock, 2 key)
-  int x32dyn = 0;        // ... written only when *dyn != 0 (the BCE target, else read as bf16)
-  unsigned char* xbits = nullptr;  // the BCE target (lock block) as bits (GemmEpi::xbits)
-  int ldbits = 0;
-  // the layer-0 pixel operand of a 0/1 batch as bits (create option bits, default on where it
-  // applies): BitMats of the forward (3B x (D + 1)) and the weight gradient ((D + 1) x 3B), written
-  // by the de-interleave instead of the bf16 plane, read by the eight-phase kernel's bits path
+  // Where the batch input stage writes (filled at plan time: plan_fp32_copies, plan_pixel_bits): xs,
+  // its planes and ldx again; f32dyn_mask, the fp32 rows written only when *dyn != 0 (the BCE target,
+  // else read as bf16); xbits / ldbits, the BCE target (lock block) as bits (GemmEpi::xbits); and,
+  // with bits_on, the layer-0 pixel operand of a 0/1 batch as bits (create option bits, default on
+  // where it applies): the BitMats of the forward (xbf, 3B x (D + 1)) and the weight gradient (xbw,
+  // (D + 1) x 3B), written by the de-interleave instead of the bf16 plane, read by the eight-phase
+  // kernel's bits path
+  BitsDst in_dst;
   bool bits_on = false;
-  unsigned* xbf = nullptr;
-  unsigned* xbw = nullptr;
-  int kts_f = 0, kts_w = 0;
   int adam_nt = 0;  // create option adam_nt
   // create option xbw_split: the de-interleave writes the forward BitMat only and the weight
   // gradient's (xbw) is transposed from it on the side stream (launch_bits_transpose), joined by

@@ -290,10 +290,13 @@ extern "C" int mvae_bench_deint(int B, int D, int variant, int iters, void* stre
   }
   int it = 0;
   const Planes pl{xp, (long long)3 * B * ldx, 1};
+  BitsDst dst;
+  dst.xbf = xbf; dst.kts_f = kf; dst.xbw = xbw; dst.kts_w = kw; dst.xbits = xb; dst.ldbits = ldbits;
+  dst.xs = xs; dst.xp = pl; dst.ldx = ldx; dst.f32dyn_mask = 2;
   auto one = [&]() -> hipError_t {
     x = xr[it++ % nx];
     if (variant == 100) return launch_deinterleave(x, xs, pl, dyn, dyn + 4, B, D, ldx, 0, 2, st, xb, ldbits);
-    return launch_deint_bits(x, B, D, xbf, kf, xbw, kw, xb, ldbits, dyn, dyn + 4, xs, pl, ldx, 2, variant == 7, st);
+    return launch_deint_bits(XBatch{x, B, D}, dst, dyn, dyn + 4, variant == 7, st);
   };
   hipEvent_t t0 = ar.event(), t1 = ar.event();
   DIAG(ar.err);
@@ -558,22 +561,21 @@ static int debug_bits(const char* caller, const unsigned char* locks, const unsi
     return fail(nullptr, MVAE_EINVAL, w + ": bad argument");
   hipStream_t st = (hipStream_t)stream;
   const int D = S * S;
-  const Planes pl{plane, (long long)3 * B * ldx, 1};
-  const int kts_f = bitmat_kts(D + 1), kts_w = bitmat_kts(3 * B);
+  BitsDst dst;  // (no fp32 rows: xs null, f32dyn_mask 0)
+  dst.xbf = xbf; dst.kts_f = bitmat_kts(D + 1); dst.xbw = xbw; dst.kts_w = bitmat_kts(3 * B);
+  dst.xbits = xbits; dst.ldbits = ldbits; dst.xp = Planes{plane, (long long)3 * B * ldx, 1}; dst.ldx = ldx;
+  int* dyn_next = dyn + 1;
+  const bool now = no_xbw != 0;
   hipError_t e;
   if (mode == 0 || mode == 3) {  // x from the tables / the caller's x, then the step's de-interleave
     const bool served = !((D % 8) || (B % 64) || (ldx % 8));
     e = mode == 0 ? launch_make_batch(locks, keys, S, S, idx, kidx, coef, B, divisor, x, st)
                   : (served ? hipSuccess : hipErrorInvalidValue);
-    if (e == hipSuccess)
-      e = launch_deint_bits(x, B, D, xbf, kts_f, xbw, kts_w, xbits, ldbits, dyn, dyn + 1, nullptr, pl, ldx, 0,
-                            no_xbw != 0, st);
+    if (e == hipSuccess) e = launch_deint_bits(XBatch{x, B, D}, dst, dyn, dyn_next, now, st);
   } else if (mode == 1) {
-    e = launch_pairs_bits(locks, keys, S, S, idx, kidx, coef, divisor, B, xbf, kts_f, xbw, kts_w, xbits, ldbits, dyn,
-                          dyn + 1, nullptr, pl, ldx, 0, no_xbw != 0, st);
+    e = launch_pairs_bits(PairsBatch{locks, keys, S, S, idx, kidx, coef, divisor, B}, dst, dyn, dyn_next, now, st);
   } else {
-    e = launch_images_bits(locks, S, S, idx, 3 * B, divisor, B, xbf, kts_f, xbw, kts_w, xbits, ldbits, dyn, dyn + 1,
-                           nullptr, pl, ldx, 0, no_xbw != 0, st);
+    e = launch_images_bits(ImagesBatch{locks, S, S, idx, 3 * B, divisor, B}, dst, dyn, dyn_next, now, st);
   }
   if (e == hipErrorInvalidValue)
     return fail(nullptr, MVAE_EINVAL, w + ": shape or alignment the kernels do not serve");

@@ -150,14 +150,14 @@ int enc_chain_rows(int M, int forced = 0);
 // K <= 512, N <= 511, 16-B aligned planes and strides multiple of 8, else hipErrorInvalidValue
 hipError_t launch_enc_chain(const ChainArgs& a, hipStream_t st);
 
-// ---- elementwise / reduction kernels (mvae_kernels.hip) ----
 // bf16 plane image of an fp32 buffer (same layout): planes at p + t*stride, t < n
 struct Planes {
   unsigned short* p = nullptr;
   long long stride = 0;
   int n = 0;
 };
-// f32mask: bit c -> write fp32 rows of block c (0 rot, 1 lock, 2 key). Plane 0 always (when
+// ---- batch input (batch_input.hip): the plane de-interleave, the bits path, the producers ----
+// The plane path. f32mask: bit c -> write fp32 rows of block c (0 rot, 1 lock, 2 key). Plane 0 always (when
 // xp.p); *dyn (zero on entry) is set when a pixel is not a bf16 value, and only then are
 // planes 1-2 (3-plane mode) and the fp32 rows of the blocks in f32dyn_mask written. The flag has
 // two slots used in turn: each launch zeroes the other one (dyn_next, the next launch's dyn),
@@ -167,22 +167,55 @@ struct Planes {
 hipError_t launch_deinterleave(const float* x, float* xs, const Planes& xp, int* dyn, int* dyn_next,
                                int B, int D, int ldx, int f32mask, int f32dyn_mask, hipStream_t st,
                                unsigned char* xbits = nullptr, int ldbits = 0);
-// The pixel operand of a 0/1 batch as bits (D % 8 == 0, B % 64 == 0): the forward BitMat xbf
-// (3B x (D + 1), kts_f = bitmat_kts(D + 1)), the weight-gradient BitMat xbw ((D + 1) x 3B, kts_w =
-// bitmat_kts(3B)) and the BCE target bits; *dyn slot 2 raised when a pixel is not 0 / 1, and then
-// (a gated second kernel) the planes of xp, the fp32 rows of f32dyn_mask and the inexact flag as
-// launch_deinterleave writes them. dyn_next: the other flag slot, zeroed. Both BitMats must be
-// zero-filled once (their padding is never written). no_xbw: the forward words only
-// (launch_bits_transpose then writes xbw from xbf).
-hipError_t launch_deint_bits(const float* x, int B, int D, unsigned* xbf, int kts_f, unsigned* xbw, int kts_w,
-                             unsigned char* xbits, int ldbits, int* dyn, int* dyn_next, float* xs,
-                             const Planes& xp, int ldx, int f32dyn_mask, bool no_xbw, hipStream_t st);
+// Where the bits path writes the layer-0 operand of a [B][D] batch: the forward BitMat xbf (3B x
+// (D + 1), kts_f = bitmat_kts(D + 1)), the weight-gradient BitMat xbw ((D + 1) x 3B, kts_w =
+// bitmat_kts(3B)), the BCE target bits (GemmEpi::xbits, ldbits >= D / 8 bytes per row) and, for a
+// batch with a pixel other than 0 / 1, what launch_deinterleave writes: the planes xp of the stacked
+// rows [3B][ldx] and the fp32 rows xs of the blocks in f32dyn_mask. Both BitMats must be zero-filled
+// once (their padding is never written). A context fills it once, at plan time (mvae_ctx::in_dst).
+struct BitsDst {
+  unsigned* xbf = nullptr; int kts_f = 0;
+  unsigned* xbw = nullptr; int kts_w = 0;
+  unsigned char* xbits = nullptr; int ldbits = 0;
+  float* xs = nullptr; Planes xp; int ldx = 0;
+  int f32dyn_mask = 0;
+};
+// The three forms of a batch. XBatch: fp32 X [B][3 D]. PairsBatch: row b is lock idx[b], its rotation
+// by coef[b] and key kidx[b], an index into `keys` (NULL: idx, the own pair); H x W images. ImagesBatch
+// (an embedding pass): 3B independent images, image t of the pass = row t of the stacked operand
+// (block t / B, batch row t % B): table image idx[t] (t when idx is null) for t < nvalid, an all-zero
+// image past that (idx not read).
+struct XBatch { const float* x; int B, D; };
+struct PairsBatch {
+  const unsigned char* locks; const unsigned char* keys; int H, W;
+  const int* idx; const int* kidx; const float* coef; float div; int B;
+};
+struct ImagesBatch { const unsigned char* table; int H, W; const int* idx; int nvalid; float div; int B; };
+// The bits path, one launcher per form; all three write the same bits for the same batch. *dyn slot 2
+// is raised when a pixel is not 0 / 1, and then (a gated second kernel) the planes, the fp32 rows and
+// the inexact flag (*dyn) are written. dyn_next: the other flag slot, zeroed. no_xbw: the forward
+// words only (launch_bits_transpose then writes xbw from xbf). Each returns hipErrorInvalidValue,
+// before anything is launched, for a batch it does not serve: D % 8 == 0 and B % 64 == 0 for all; a
+// 16-byte aligned x; 8-byte aligned tables and a 16-byte aligned coef (pairs_bits_fits,
+// images_bits_fits).
+hipError_t launch_deint_bits(const XBatch& src, const BitsDst& dst, int* dyn, int* dyn_next, bool no_xbw,
+                             hipStream_t st);
+bool pairs_bits_fits(const unsigned char* locks, const unsigned char* keys, const float* coef, int B, int D);
+hipError_t launch_pairs_bits(const PairsBatch& src, const BitsDst& dst, int* dyn, int* dyn_next, bool no_xbw,
+                             hipStream_t st);
+bool images_bits_fits(const unsigned char* table, int B, int D);
+hipError_t launch_images_bits(const ImagesBatch& src, const BitsDst& dst, int* dyn, int* dyn_next, bool no_xbw,
+                              hipStream_t st);
 // the weight gradient's BitMat xbw from the forward's xbf (both of a 3B-row batch; see
 // bits_transpose_kernel)
 hipError_t launch_bits_transpose(const unsigned* xbf, int kts_f, unsigned* xbw, int kts_w, int B, hipStream_t st);
-// the grey pass alone
-hipError_t launch_deint_grey(const float* x, int B, int D, int* dyn, float* xs, const Planes& xp, int ldx,
-                             int f32dyn_mask, hipStream_t st);
+// The producers: a pairs batch / an embedding pass as X [B][3 D] (any D, any alignment):
+// x[b, 3 p + ch] = (lock, rotated lock, key)[ch] / div, for a pass image((1, 0, 2)[ch] B + b)[p] / div
+hipError_t launch_make_batch(const unsigned char* locks, const unsigned char* keys, int H, int W,
+                             const int* idx, const int* kidx, const float* coef, int B, float div, float* x,
+                             hipStream_t st);  // kidx: the key of each row; NULL: idx
+hipError_t launch_images_x(const ImagesBatch& src, float* x, hipStream_t st);
+// ---- elementwise / reduction kernels (mvae_kernels.hip) ----
 // N(0,1) into out[slots][B][L]: elements (s*Bg + off + b)*L + l of the counter's global stream
 // (Bg rows per slot over all ranks, this rank's rows starting at off)
 hipError_t launch_normal(float* out, int slots, int B, int L, int Bg, int off, uint64_t seed,
@@ -225,35 +258,6 @@ hipError_t launch_adam(const AdamArgs& a, hipStream_t st);
 hipError_t launch_split_planes(const float* src, size_t n, const Planes& dst, hipStream_t st);
 // x[i] = x[i] > 0 ? 1 : 0 (diagnostics: binary BCE targets for the GEMM harness)
 hipError_t launch_binarize(float* x, size_t n, hipStream_t st);
-hipError_t launch_make_batch(const unsigned char* locks, const unsigned char* keys, int H, int W,
-                             const int* idx, const int* kidx, const float* coef, int B, float div, float* x,
-                             hipStream_t st);  // kidx: the key of each row; NULL: idx
-// ---- a batch's bit operands straight from the uint8 tables (pairs_bits.hip) ----
-// What launch_make_batch followed by launch_deint_bits writes (the same bits: BitMats, target
-// bits, flag slots, and for a batch with a pixel other than 0 / 1 the planes, fp32 rows and inexact
-// flag of the grey pass), without X. no_xbw: the forward words only (as launch_deint_bits').
-// Serves D = H W % 8 == 0, B % 64 == 0, 8-byte aligned tables and a 16-byte aligned coef
-// (pairs_bits_fits); hipErrorInvalidValue otherwise, before anything is launched. kidx: the key of
-// each row, an index into `keys` (NULL: idx, the own pair).
-bool pairs_bits_fits(const unsigned char* locks, const unsigned char* keys, const float* coef, int B, int D);
-hipError_t launch_pairs_bits(const unsigned char* locks, const unsigned char* keys, int H, int W, const int* idx,
-                             const int* kidx, const float* coef, float div, int B, unsigned* xbf, int kts_f,
-                             unsigned* xbw, int kts_w, unsigned char* xbits, int ldbits, int* dyn, int* dyn_next,
-                             float* xs, const Planes& xp, int ldx, int f32dyn_mask, bool no_xbw, hipStream_t st);
-// ---- an embedding pass's operand from one uint8 image table (images_bits.hip) ----
-// 3B independent images, image t of the pass = row t of the stacked operand (block t / B, batch row
-// t % B): table image idx[t] (t when idx is null) for t < nvalid, an all-zero image past that (idx
-// not read). launch_images_bits writes what launch_images_x followed by launch_deint_bits writes
-// (no_xbw: likewise) and serves D % 8 == 0, B % 64 == 0 and an 8-byte aligned table
-// (images_bits_fits; hipErrorInvalidValue otherwise, before anything is launched); launch_images_x
-// writes the pass as X [B][3 D]: x[b, 3 p + ch] = image((1, 0, 2)[ch] B + b)[p] / div.
-bool images_bits_fits(const unsigned char* table, int B, int D);
-hipError_t launch_images_bits(const unsigned char* table, int H, int W, const int* idx, int nvalid, float div, int B,
-                              unsigned* xbf, int kts_f, unsigned* xbw, int kts_w, unsigned char* xbits, int ldbits,
-                              int* dyn, int* dyn_next, float* xs, const Planes& xp, int ldx, int f32dyn_mask,
-                              bool no_xbw, hipStream_t st);
-hipError_t launch_images_x(const unsigned char* table, int H, int W, const int* idx, int nvalid, float div, int B,
-                           float* x, hipStream_t st);
 // ---- all-pairs distance with fused top-k (match.hip) ----
 // match_plan: key rows per split (a multiple of 64) and the number of splits of M for N lock rows.
 void match_plan(long long N, long long M, long long* split_len, int* splits);

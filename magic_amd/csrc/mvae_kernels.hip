@@ -1,13 +1,12 @@
-// Bandwidth-bound kernels of the metric-VAE step (gfx950): batch de-interleave, the
-// counter-based N(0,1) sampler, reparameterisation, the latent loss head forward/backward
-// (KL, deformation, cosine / squared-difference distance, training_loss), deterministic
-// loss/column reductions, and the fused dual TF-Adam update.
+// Bandwidth-bound kernels of the metric-VAE step (gfx950): the counter-based N(0,1) sampler,
+// reparameterisation, the latent loss head forward/backward (KL, deformation, cosine /
+// squared-difference distance, training_loss), deterministic loss/column reductions, the fused
+// dual TF-Adam update and the small copies. (The batch's way into the step: batch_input.hip.)
 //
 // Row order of every stacked encoder buffer: [rotated lock | lock | key] (3B rows), so the
 // cost gradient (rotated+lock) and the metric gradient (lock+key) each use a CONTIGUOUS
 // 2B-row range. The backward stacks 4B rows: [rot(g1) | lock(g1) | lock(g2) | key(g2)].
 #include "mvae_internal.h"
-#include "deint_bits.h"
 #include <cstdlib>
 
 namespace mvae {
@@ -32,157 +31,6 @@ __device__ __forceinline__ bool planes_put(unsigned short* p, long long ps, int 
 
 // internal block (0 rot, 1 lock, 2 key) -> reference eps slot (0 lock, 1 rot, 2 key)
 __device__ __forceinline__ int eps_slot(int blk) { return blk == 0 ? 1 : (blk == 1 ? 0 : 2); }
-
-// ---------------------------------------------------------------- de-interleave
-// x[b][p*3 + c] (c: 0 lock, 1 rotated lock, 2 key; 11a/overlap_input.py:117-119,201)
-//  -> xs[(blk*B + b)][p], blk = {rot:0, lock:1, key:2}. Each thread moves 4 pixels:
-// three 16-B loads, three 16-B stores (coalesced both ways).
-// (bf16_rn, pack4: deint_bits.h)
-
-// [B, D, 3] interleaved (lock, rotated, key) -> row blocks [rot | lock | key] of the layer-0
-// operand: fp32 rows for the blocks in f32mask (bit c: block c; plane modes keep only the lock
-// block, the BCE target) and the RN bf16 plane 0 (8-byte stores). In the exact-split mode the
-// residual planes are NOT written here: the kernel only raises *dyn when some pixel is not
-// exact in bf16, and residual_planes_kernel then writes planes 1 and 2 (binary shape images
-// never pay for them; the GEMMs read the residual planes only when *dyn != 0).
-__global__ void deinterleave_vec_kernel(const float4* __restrict__ x, float* __restrict__ xs,
-                                        unsigned short* __restrict__ xp, int* __restrict__ dyn,
-                                        int B, int D, int ldx, int f32mask, int* __restrict__ dyn_next) {
-  // the other slot of the flags, for the next de-interleave (no per-step memset launch); this
-  // form does not test for 0/1 pixels: it raises the not-binary word (dyn[2]) unconditionally
-  if ((blockIdx.x | blockIdx.y | threadIdx.x) == 0) {
-    if (dyn_next) dyn_next[0] = dyn_next[2] = 0;
-    if (dyn) atomicOr(dyn + 2, 1);
-  }
-  const int b = blockIdx.y;
-  const int q = blockIdx.x * blockDim.x + threadIdx.x;  // pixel quad
-  bool nz = false;
-  if (q * 4 < D) {
-    const float4* src = x + ((size_t)b * 3 * D) / 4 + 3 * q;
-    const float4 v0 = src[0], v1 = src[1], v2 = src[2];
-    // pixels p0..p3: (l,r,k) = (v0.x v0.y v0.z) (v0.w v1.x v1.y) (v1.z v1.w v2.x) (v2.y v2.z v2.w)
-    const float4 vv[3] = {make_float4(v0.y, v1.x, v1.w, v2.z),   // rot
-                          make_float4(v0.x, v0.w, v1.z, v2.y),   // lock
-                          make_float4(v0.z, v1.y, v2.x, v2.w)};  // key
-    const size_t col = 4 * (size_t)q;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const size_t o = (size_t)(c * B + b) * ldx + col;
-      if (f32mask >> c & 1) *reinterpret_cast<float4*>(xs + o) = vv[c];
-      if (xp) {
-        float r0, r1, r2, r3;
-        const uint2 w = pack4(bf16_rn(vv[c].x, r0), bf16_rn(vv[c].y, r1), bf16_rn(vv[c].z, r2),
-                              bf16_rn(vv[c].w, r3));
-        *reinterpret_cast<uint2*>(xp + o) = w;
-        nz |= (r0 != 0.f) | (r1 != 0.f) | (r2 != 0.f) | (r3 != 0.f);
-      }
-    }
-  }
-  if (dyn && __ballot(nz) != 0 && (threadIdx.x & 63) == 0) atomicOr(dyn, 1);
-}
-
-// The same for 4 NQ pixels per thread (D % (4 NQ) == 0): 3 NQ 16-B loads (48 NQ contiguous
-// bytes) issued together, then per block NQ / 2 16-B plane stores. 8 pixels per thread measured
-// 0.305 -> 0.287 ms at C3 (profiles/r4/r4y_deinterleave.txt)
-template <int NQ>
-__global__ void deinterleave_vecn_kernel(const float4* __restrict__ x, float* __restrict__ xs,
-                                         unsigned short* __restrict__ xp, int* __restrict__ dyn,
-                                         int B, int D, int ldx, int f32mask, int* __restrict__ dyn_next,
-                                         unsigned char* __restrict__ xbits, int ldbits) {
-  // the other slot of the flags, for the next de-interleave (no per-step memset launch)
-  if (dyn_next && (blockIdx.x | blockIdx.y | threadIdx.x) == 0) dyn_next[0] = dyn_next[2] = 0;
-  constexpr int NP = 4 * NQ;  // pixels per thread
-  const int b = blockIdx.y;
-  const int q = blockIdx.x * blockDim.x + threadIdx.x;
-  bool nz = false, nb = false;
-  if (q * NP < D) {
-    const float4* src = x + ((size_t)b * 3 * D) / 4 + 3 * NQ * q;
-    float4 v[3 * NQ];
-#pragma unroll
-    for (int i = 0; i < 3 * NQ; ++i) v[i] = src[i];
-    // some value of the three channels neither 0 nor 1 (the BCE target is one of them)
-#pragma unroll
-    for (int i = 0; i < 3 * NQ; ++i) {
-      const float e[4] = {v[i].x, v[i].y, v[i].z, v[i].w};
-#pragma unroll
-      for (int j = 0; j < 4; ++j) nb |= (e[j] != 0.f) & (e[j] != 1.f);
-    }
-    nz = deint_put<NQ>(v, xs, xp, B, b, (size_t)NP * q, ldx, f32mask);
-    if (xbits) {  // the lock channel (element 3 j of pixel j) as bits, 8 pixels per byte
-      static_assert(NQ == 2, "one byte per thread");
-      const float e[24] = {v[0].x, v[0].y, v[0].z, v[0].w, v[1].x, v[1].y, v[1].z, v[1].w,
-                           v[2].x, v[2].y, v[2].z, v[2].w, v[3].x, v[3].y, v[3].z, v[3].w,
-                           v[4].x, v[4].y, v[4].z, v[4].w, v[5].x, v[5].y, v[5].z, v[5].w};
-      unsigned byte = 0;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) byte |= (e[3 * j] != 0.f ? 1u : 0u) << j;
-      xbits[(size_t)b * ldbits + q] = (unsigned char)byte;
-    }
-  }
-  if (dyn) {  // (the ballots with every lane of the wave active)
-    const bool anz = __ballot(nz) != 0, anb = __ballot(nb) != 0;
-    if ((threadIdx.x & 63) == 0) {
-      if (anz) atomicOr(dyn, 1);
-      if (anb) atomicOr(dyn + 2, 1);
-    }
-  }
-}
-
-__global__ void deinterleave_scalar_kernel(const float* __restrict__ x, float* __restrict__ xs,
-                                           unsigned short* __restrict__ xp, int* __restrict__ dyn,
-                                           int B, int D, int ldx, int f32mask, int* __restrict__ dyn_next) {
-  // the other slot of the flags (see deinterleave_vec_kernel: no 0/1 test here)
-  if ((blockIdx.x | blockIdx.y | threadIdx.x) == 0) {
-    if (dyn_next) dyn_next[0] = dyn_next[2] = 0;
-    if (dyn) atomicOr(dyn + 2, 1);
-  }
-  const int b = blockIdx.y;
-  const int p = blockIdx.x * blockDim.x + threadIdx.x;
-  bool nz = false;
-  if (p < D) {
-    const float* src = x + (size_t)b * 3 * D + 3 * (size_t)p;
-    const float v[3] = {src[1], src[0], src[2]};  // rot, lock, key
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const size_t o = (size_t)(c * B + b) * ldx + p;
-      if (f32mask >> c & 1) xs[o] = v[c];
-      if (xp) {
-        float r;
-        xp[o] = bf16_rn(v[c], r);
-        nz |= r != 0.f;
-      }
-    }
-  }
-  if (dyn && __ballot(nz) != 0 && (threadIdx.x & 63) == 0) atomicOr(dyn, 1);
-}
-
-// Only when *dyn != 0 (some pixel of the batch is not a bf16 value): planes 1 and 2 of the
-// exact split of the layer-0 operand (3-plane mode), and the fp32 rows of the blocks in
-// f32mask (the BCE target, read from bf16 plane 0 while every pixel is exact).
-__global__ void residual_planes_kernel(const float* __restrict__ x, float* __restrict__ xs,
-                                       unsigned short* __restrict__ xp, long long ps, int np,
-                                       int f32mask, const int* __restrict__ dyn, int B, int D,
-                                       int ldx) {
-  if (*dyn == 0) return;
-  const size_t n = (size_t)B * D;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += (size_t)gridDim.x * blockDim.x) {
-    const size_t b = i / D, p = i - b * D;
-    const float* src = x + b * 3 * D + 3 * p;
-    const float v[3] = {src[1], src[0], src[2]};  // rot, lock, key
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const size_t o = (size_t)(c * B + b) * ldx + p;
-      if (f32mask >> c & 1) xs[o] = v[c];
-      if (np == 3) {
-        float r1, r2, r3;
-        (void)bf16_rn(v[c], r1);
-        xp[ps + o] = bf16_rn(r1, r2);
-        xp[2 * ps + o] = bf16_rn(r2, r3);
-      }
-    }
-  }
-}
 
 // ---------------------------------------------------------------- N(0,1) sampler
 // Philox4x32-10 counter-based generator + Box-Muller; element i of call `counter` depends
@@ -302,7 +150,8 @@ __device__ __forceinline__ void planes_put4(unsigned short* p, long long ps, int
       q[j] = __builtin_bit_cast(unsigned short, __float2bfloat16(r[j]));
       r[j] -= __uint_as_float((unsigned)q[j] << 16);
     }
-    *reinterpret_cast<uint2*>(p + t * ps + o) = pack4(q[0], q[1], q[2], q[3]);
+    *reinterpret_cast<uint2*>(p + t * ps + o) =
+        make_uint2((unsigned)q[0] | (unsigned)q[1] << 16, (unsigned)q[2] | (unsigned)q[3] << 16);
   }
 }
 
@@ -721,263 +570,11 @@ __global__ void copy2d_kernel(const float* __restrict__ s, int lds, float* __res
   d[(size_t)r * ldd + c] = s[(size_t)r * lds + c];
 }
 
-// ---------------------------------------------------------------- batch producer
-// The reference's input pipeline for one batch (11a/overlap_input.py:127-261): lock and key
-// images from uint8 tables, the lock rotated by tf.contrib.image.rotate semantics (output
-// (x,y) samples ((c*x - s*y) + x_off, (s*x + c*y) + y_off), NEAREST = roundf, zero fill;
-// per-example coefficients precomputed in fp32 on the host), concatenated per pixel as
-// (lock, rotated, key) and divided by 255 -> X [B, H*W*3]. No FMA contraction, so the
-// gather indices match the host restatement bit for bit (hipcc contracts even the *_rn
-// intrinsics into FMAs unless contraction is off: a few pixels per batch then sampled a
-// neighbour; caught by tests/test_input_pipeline.py's grey-value tables).
-// Row b is lock idx[b], its rotation, and key kidx[b] (the own pair passes idx for both).
-__global__ void make_batch_kernel(const unsigned char* __restrict__ locks,
-                                  const unsigned char* __restrict__ keys, int H, int W,
-                                  const int* __restrict__ idx, const int* __restrict__ kidx,
-                                  const float4* __restrict__ coef, float div, float* __restrict__ x) {
-#pragma clang fp contract(off)  // (the *_rn intrinsics do not prevent it: their bodies are outside)
-  const int b = blockIdx.y;
-  const int p = blockIdx.x * blockDim.x + threadIdx.x;
-  const int HW = H * W;
-  if (p >= HW) return;
-  const int id = idx[b], kid = kidx[b];
-  const float4 cf = coef[b];
-  // (the row's three scalar loads in flight together and waited for once: left to itself the
-  // scheduler issues the key's index or the coefficients only after waiting for the lock's index, a
-  // second round trip at the head of a short workgroup)
-  asm volatile("" ::"s"(id), "s"(kid), "s"(cf.x), "s"(cf.y), "s"(cf.z), "s"(cf.w));
-  const int yy = p / W, xx = p - yy * W;
-  const float fx = (float)xx, fy = (float)yy;
-  const float xin = (cf.x * fx - cf.y * fy) + cf.z;  // unfused: fp contract(off) above
-  const float yin = (cf.y * fx + cf.x * fy) + cf.w;
-  const float xr = roundf(xin), yr = roundf(yin);
-  const unsigned char* L = locks + (size_t)id * HW;
-  float rot = 0.f;
-  if (xr >= 0.f && xr <= (float)(W - 1) && yr >= 0.f && yr <= (float)(H - 1))
-    rot = (float)L[(int)yr * W + (int)xr];
-  float* o = x + (size_t)b * 3 * HW + 3 * (size_t)p;
-  o[0] = (float)L[p] / div;
-  o[1] = rot / div;
-  o[2] = (float)keys[(size_t)kid * HW + p] / div;
-}
-
-// The same batch (bit for bit) at 4 pixels per thread for H*W % 4 == 0 and a 16-B aligned x:
-// one 4-B load each of the lock and key bytes, the 12 output floats of a thread written to LDS,
-// and the workgroup's 1024-pixel segment of the output row (12 KB, contiguous in x) stored back
-// with 16-B stores that are contiguous across each wave (3 per thread). The per-pixel store of
-// make_batch_kernel (three 4-B stores at a 12-B lane stride) ran at ~2.1-2.5 TB/s.
-constexpr int MB_PIX = 4 * 256;  // pixels per workgroup
-__global__ __launch_bounds__(256) void make_batch4_kernel(const unsigned char* __restrict__ locks,
-                                                          const unsigned char* __restrict__ keys, int H,
-                                                          int W, const int* __restrict__ idx,
-                                                          const int* __restrict__ kidx,
-                                                          const float4* __restrict__ coef, float div,
-                                                          float* __restrict__ x) {
-#pragma clang fp contract(off)  // as make_batch_kernel: the coordinates are unfused mul / add / sub
-  __shared__ __attribute__((aligned(16))) float seg[3 * MB_PIX];
-  const int b = blockIdx.y;
-  const int tid = threadIdx.x;
-  const int HW = H * W;
-  const int s0 = blockIdx.x * MB_PIX;  // first pixel of the segment
-  const int p0 = s0 + 4 * tid;
-  const int id = idx[b], kid = kidx[b];
-  const float4 cf = coef[b];
-  // (the row's three scalar loads in flight together and waited for once: left to itself the
-  // scheduler issues the key's index or the coefficients only after waiting for the lock's index, a
-  // second round trip at the head of a short workgroup)
-  asm volatile("" ::"s"(id), "s"(kid), "s"(cf.x), "s"(cf.y), "s"(cf.z), "s"(cf.w));
-  const unsigned char* L = locks + (size_t)id * HW;
-  if (p0 < HW) {
-    const uchar4 lv = *reinterpret_cast<const uchar4*>(L + p0);
-    const uchar4 kv = *reinterpret_cast<const uchar4*>(keys + (size_t)kid * HW + p0);
-    const unsigned char l[4] = {lv.x, lv.y, lv.z, lv.w}, k[4] = {kv.x, kv.y, kv.z, kv.w};
-    float v[12];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int p = p0 + j;
-      const int yy = p / W, xx = p - yy * W;
-      const float fx = (float)xx, fy = (float)yy;
-      const float xin = (cf.x * fx - cf.y * fy) + cf.z;  // unfused: fp contract(off) above
-      const float yin = (cf.y * fx + cf.x * fy) + cf.w;
-      const float xr = roundf(xin), yr = roundf(yin);
-      float rot = 0.f;
-      if (xr >= 0.f && xr <= (float)(W - 1) && yr >= 0.f && yr <= (float)(H - 1))
-        rot = (float)L[(int)yr * W + (int)xr];
-      v[3 * j] = (float)l[j] / div;
-      v[3 * j + 1] = rot / div;
-      v[3 * j + 2] = (float)k[j] / div;
-    }
-    float4* d = reinterpret_cast<float4*>(seg + 12 * tid);
-    d[0] = make_float4(v[0], v[1], v[2], v[3]);
-    d[1] = make_float4(v[4], v[5], v[6], v[7]);
-    d[2] = make_float4(v[8], v[9], v[10], v[11]);
-  }
-  __syncthreads();
-  const int nf = 3 * min(MB_PIX, HW - s0);  // floats of this segment (a multiple of 12)
-  float4* o = reinterpret_cast<float4*>(x + (size_t)b * 3 * HW + 3 * (size_t)s0);
-#pragma unroll
-  for (int s = 0; s < 3; ++s) {
-    const int f = 4 * (tid + 256 * s);
-    if (f < nf) o[tid + 256 * s] = *reinterpret_cast<const float4*>(seg + f);
-  }
-}
-
-// ---------------------------------------------------------------- de-interleave to bits
-// The layer-0 pixel operand of a 0/1 batch as BitMats (deint_bits.h): one workgroup per task of
-// 64 batch rows x 64 PB pixels. Raises the not-binary word (*dyn slot 2) when a pixel is neither 0
-// nor 1: the step then runs deint_grey_kernel (the planes) and the GEMMs read the planes.
-template <int PB, int NT, int OS, bool NOW = false>
-__global__ __launch_bounds__(NT) void deint_bits_kernel(const float4* __restrict__ x, int B, int D, int kts_f,
-                                                        int kts_w, unsigned* __restrict__ xbf,
-                                                        unsigned* __restrict__ xbw,
-                                                        unsigned char* __restrict__ xbits, int ldbits,
-                                                        int* __restrict__ dyn, int* __restrict__ dyn_next) {
-  if (dyn_next && (blockIdx.x | blockIdx.y | threadIdx.x) == 0) dyn_next[0] = dyn_next[2] = 0;
-  __shared__ __attribute__((aligned(16))) DeintLds<PB, OS> bt;
-  deint_bits_task<PB, NT, OS, NOW>(x, B, D, kts_f, kts_w, xbf, xbw, xbits, ldbits, dyn, blockIdx.x, blockIdx.y, bt);
-}
-
-// The weight gradient's BitMat (pixels x stacked rows) from the forward's (stacked rows x
-// pixels): one wave per 64 x 64 bit tile -- a quarter of a block on either side -- its 128 words in,
-// the tile as [8 pixel octets][64 rows] bytes in LDS, its 128 transposed words out (the 8 x 8 bit
-// transpose of deint_bits.h). The de-interleave then writes only the forward words
-// (launch_deint_bits with no_xbw): the transpose runs on the side stream beside the layer-0 forward, whose 192 tiles
-// (C3) leave CUs free, and the layer-0 weight gradient waits for it.
-__device__ __forceinline__ unsigned bits_compact(unsigned s) {  // inverse of bits_spread (low byte)
-  unsigned e = s & 0xFu, o = (s >> 16) & 0xFu;
-  e = (e | (e << 2)) & 0x33u; e = (e | (e << 1)) & 0x55u;
-  o = (o | (o << 2)) & 0x33u; o = (o | (o << 1)) & 0x55u;
-  return e | (o << 1);
-}
-__global__ __launch_bounds__(256) void bits_transpose_kernel(const unsigned* __restrict__ xbf, int kts_f,
-                                                             unsigned* __restrict__ xbw, int kts_w, int nrow64) {
-  __shared__ __attribute__((aligned(16))) unsigned char tb[4][8][64];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int tile = blockIdx.x * 4 + wave;
-  const bool ok = tile < nrow64 * kts_f;
-  const int a = ok ? tile % nrow64 : 0, b = ok ? tile / nrow64 : 0;  // stacked-row tile, pixel tile
-  if (ok) {
-    const uint2 w = *reinterpret_cast<const uint2*>(xbf + ((size_t)(a >> 2) * kts_f + b) * BITMAT_BLOCK_WORDS +
-                                                    (a & 3) * 128 + 2 * lane);
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int h = 0; h < 2; ++h)
-#pragma unroll
-        for (int kh = 0; kh < 2; ++kh)
-          tb[wave][4 * kh + (lane >> 4)][16 * (2 * j + h) + (lane & 15)] =
-              (unsigned char)bits_compact((j ? w.y : w.x) >> (8 * h + 4 * kh));
-  }
-  __syncthreads();
-  if (!ok) return;
-  unsigned out[2];
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    unsigned wo = 0;
-#pragma unroll
-    for (int h = 0; h < 2; ++h)
-#pragma unroll
-      for (int kh = 0; kh < 2; ++kh) {
-        const int p = 16 * (2 * j + h) + (lane & 15);
-        const unsigned long long rows =
-            *reinterpret_cast<const unsigned long long*>(&tb[wave][p >> 3][32 * kh + 8 * (lane >> 4)]);
-        const unsigned long long col = (rows >> (p & 7)) & 0x0101010101010101ull;
-        wo |= bits_spread((unsigned)((col * 0x0102040810204080ull) >> 56)) << (8 * h + 4 * kh);
-      }
-    out[j] = wo;
-  }
-  *reinterpret_cast<uint2*>(xbw + ((size_t)(b >> 2) * kts_w + a) * BITMAT_BLOCK_WORDS + (b & 3) * 128 + 2 * lane) =
-      make_uint2(out[0], out[1]);
-}
-
-// The plane image of a batch with a pixel other than 0 or 1 (after deint_bits_kernel raised the
-// not-binary word; else every workgroup returns at once): bf16 plane 0 (planes 1-2 of the exact
-// split too when np == 3), the fp32 rows of the blocks in f32mask, and the inexact flag (*dyn) --
-// what the plane path's GEMMs and the BCE epilogue read. Workgroups stride over the 8-pixel groups.
-__global__ void deint_grey_kernel(const float4* __restrict__ x, float* __restrict__ xs,
-                                  unsigned short* __restrict__ xp, long long ps, int np, int f32mask,
-                                  int* __restrict__ dyn, int B, int D, int ldx) {
-  if (dyn[2] == 0) return;
-  const int nq = D / 8;
-  const size_t n = (size_t)B * nq;
-  bool nz = false;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    const int b = (int)(i / nq), q = (int)(i % nq);
-    const float4* src = x + ((size_t)b * 3 * D) / 4 + 6 * (size_t)q;
-    float4 v[6];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) v[k] = src[k];
-    nz |= deint_grey_octet(v, xs, xp, ps, np, f32mask, B, b, q, ldx);
-  }
-  if (__ballot(nz) != 0 && (threadIdx.x & 63) == 0) atomicOr(dyn, 1);
-}
-
 inline unsigned nblocks(size_t n, int bs) { return (unsigned)((n + bs - 1) / bs); }
 
 __global__ void mvae_region_marker() {}
 
 }  // namespace
-
-hipError_t launch_deinterleave(const float* x, float* xs, const Planes& xp, int* dyn, int* dyn_next,
-                               int B, int D, int ldx, int f32mask, int f32dyn_mask, hipStream_t st,
-                               unsigned char* xbits, int ldbits) {
-  // 8 pixels per thread (4 and 16 measured slower, profiles/r4/r4y_deinterleave.txt; an LDS-staged
-  // form with lane-contiguous loads too, r4an_deinterleave_lds_rejected.txt); 4 when D % 8 != 0
-  const bool al = (reinterpret_cast<uintptr_t>(x) % 16) == 0;
-  if ((D % 8) == 0 && al && (ldx % 8) == 0) {
-    dim3 g(nblocks(D / 8, 256), B);
-    hipLaunchKernelGGL(deinterleave_vecn_kernel<2>, g, dim3(256), 0, st,
-                       reinterpret_cast<const float4*>(x), xs, xp.p, dyn, B, D, ldx, f32mask, dyn_next,
-                       xbits, ldbits);
-  } else if ((D % 4) == 0 && (reinterpret_cast<uintptr_t>(x) % 16) == 0 && (ldx % 4) == 0) {
-    dim3 g(nblocks(D / 4, 256), B);
-    hipLaunchKernelGGL(deinterleave_vec_kernel, g, dim3(256), 0, st,
-                       reinterpret_cast<const float4*>(x), xs, xp.p, dyn, B, D, ldx, f32mask, dyn_next);
-  } else {
-    dim3 g(nblocks(D, 256), B);
-    hipLaunchKernelGGL(deinterleave_scalar_kernel, g, dim3(256), 0, st, x, xs, xp.p, dyn, B, D, ldx,
-                       f32mask, dyn_next);
-  }
-  f32dyn_mask &= ~f32mask;
-  if (dyn && xp.p && (xp.n == 3 || f32dyn_mask))
-    hipLaunchKernelGGL(residual_planes_kernel, dim3(2048), dim3(256), 0, st, x, xs, xp.p, xp.stride,
-                       xp.n, f32dyn_mask, dyn, B, D, ldx);
-  return hipGetLastError();
-}
-
-hipError_t launch_deint_bits(const float* x, int B, int D, unsigned* xbf, int kts_f, unsigned* xbw, int kts_w,
-                             unsigned char* xbits, int ldbits, int* dyn, int* dyn_next, float* xs,
-                             const Planes& xp, int ldx, int f32dyn_mask, bool no_xbw, hipStream_t st) {
-  if ((D % 8) || (B % 64) || (reinterpret_cast<uintptr_t>(x) % 16) || (ldx % 8) || !dyn || !xp.p ||
-      kts_f != bitmat_kts(D + 1) || kts_w != bitmat_kts(3 * B))
-    return hipErrorInvalidValue;
-  const float4* x4 = reinterpret_cast<const float4*>(x);
-  const dim3 grid((kts_f + 1) / 2, B / 64);
-  if (no_xbw)  // without the weight-gradient words (launch_bits_transpose writes them)
-    hipLaunchKernelGGL((deint_bits_kernel<2, 256, 72, true>), grid, dim3(256), 0, st, x4, B, D, kts_f, kts_w, xbf, xbw,
-                       xbits, ldbits, dyn, dyn_next);
-  else
-    hipLaunchKernelGGL((deint_bits_kernel<2, 256, 72>), grid, dim3(256), 0, st, x4, B, D, kts_f, kts_w, xbf, xbw, xbits,
-                       ldbits, dyn, dyn_next);
-  return launch_deint_grey(x, B, D, dyn, xs, xp, ldx, f32dyn_mask, st);
-}
-
-hipError_t launch_bits_transpose(const unsigned* xbf, int kts_f, unsigned* xbw, int kts_w, int B, hipStream_t st) {
-  if (B % 64 || kts_f <= 0 || kts_w != bitmat_kts(3 * B)) return hipErrorInvalidValue;
-  const int nrow64 = 3 * B / 64;
-  const long long tiles = (long long)nrow64 * kts_f;
-  hipLaunchKernelGGL(bits_transpose_kernel, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, st, xbf, kts_f, xbw,
-                     kts_w, nrow64);
-  return hipGetLastError();
-}
-
-hipError_t launch_deint_grey(const float* x, int B, int D, int* dyn, float* xs, const Planes& xp, int ldx,
-                             int f32dyn_mask, hipStream_t st) {
-  // (256 workgroups striding: for a 0/1 batch every one returns at once, and fewer cost less)
-  hipLaunchKernelGGL(deint_grey_kernel, dim3(256), dim3(256), 0, st, reinterpret_cast<const float4*>(x), xs,
-                     xp.p, xp.stride, xp.n, f32dyn_mask, dyn, B, D, ldx);
-  return hipGetLastError();
-}
 
 hipError_t launch_normal(float* out, int slots, int B, int L, int Bg, int off, uint64_t seed,
                          uint64_t counter, hipStream_t st) {
@@ -1081,23 +678,6 @@ __global__ void binarize_kernel(float* x, size_t n) {
 hipError_t launch_binarize(float* x, size_t n, hipStream_t st) {
   if (n == 0) return hipSuccess;
   hipLaunchKernelGGL(binarize_kernel, dim3(nblocks(n, 256)), dim3(256), 0, st, x, n);
-  return hipGetLastError();
-}
-
-hipError_t launch_make_batch(const unsigned char* locks, const unsigned char* keys, int H, int W,
-                             const int* idx, const int* kidx, const float* coef, int B, float div, float* x,
-                             hipStream_t st) {
-  if (!kidx) kidx = idx;  // the own pair
-  const size_t hw = (size_t)H * W;
-  if (hw % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0) {
-    dim3 g(nblocks(hw, MB_PIX), B);
-    hipLaunchKernelGGL(make_batch4_kernel, g, dim3(256), 0, st, locks, keys, H, W, idx, kidx,
-                       reinterpret_cast<const float4*>(coef), div, x);
-    return hipGetLastError();
-  }
-  dim3 g(nblocks(hw, 256), B);
-  hipLaunchKernelGGL(make_batch_kernel, g, dim3(256), 0, st, locks, keys, H, W, idx, kidx,
-                     reinterpret_cast<const float4*>(coef), div, x);
   return hipGetLastError();
 }
 

@@ -456,7 +456,7 @@ int wire_gemms(mvae_ctx* c, const CreateOpts& opt) {
   return MVAE_OK;
 }
 
-// which fp32 copies the step writes beside the plane images: x32mask / x32dyn (pixel rows), the
+// which fp32 copies the step writes beside the plane images: x32mask / in_dst.f32dyn_mask (pixel rows), the
 // BCE target's bits, c32 of every GEMM output, zmask, dhead32, xf32
 int plan_fp32_copies(mvae_ctx* c, const CreateOpts&) {
   const size_t B = c->B;
@@ -465,7 +465,7 @@ int plan_fp32_copies(mvae_ctx* c, const CreateOpts&) {
   // reads plane 0 while *dyn == 0)
   if (c->np) {
     c->x32mask = 0;
-    c->x32dyn = 2;
+    c->in_dst.f32dyn_mask = 2;
     // (the encoder's forward and backward only: no other GEMM of the schedule has xs as its A
     // operand -- the BCE head reads it through its epilogue, handled below)
     for (auto* v : {&c->fwd_enc, &c->bwd_enc})
@@ -477,10 +477,10 @@ int plan_fp32_copies(mvae_ctx* c, const CreateOpts&) {
       c->f_out.epi.xdyn = c->dyn;
       c->f_out.epi.xnb = c->dyn + 2;
       if (c->D % 8 == 0) {  // the 8-pixel de-interleave writes the target's bits beside its plane
-        c->ldbits = (c->D / 8 + 15) & ~15;
-        PLAN_ALLOC(c->xbits, B * c->ldbits);
-        c->f_out.epi.xbits = c->xbits;
-        c->f_out.epi.ldbits = c->ldbits;
+        c->in_dst.ldbits = (c->D / 8 + 15) & ~15;
+        PLAN_ALLOC(c->in_dst.xbits, B * c->in_dst.ldbits);
+        c->f_out.epi.xbits = c->in_dst.xbits;
+        c->f_out.epi.ldbits = c->in_dst.ldbits;
       }
     } else {
       c->x32mask |= 2;  // the native fp32 BCE GEMM reads the fp32 target rows
@@ -524,6 +524,9 @@ int plan_fp32_copies(mvae_ctx* c, const CreateOpts&) {
   for (auto* v : {&c->fwd_enc, &c->bwd_dec, &c->bwd_enc})
     for (auto& d : *v)
       if (c->np && (!d.Ap || !d.Bp)) return fail(nullptr, MVAE_EINVAL, "internal: GEMM operand without plane image");
+  c->in_dst.xs = c->xs;
+  c->in_dst.xp = planes_of(c, c->xs);
+  c->in_dst.ldx = c->ldx;
   return MVAE_OK;
 }
 
@@ -532,16 +535,17 @@ int plan_fp32_copies(mvae_ctx* c, const CreateOpts&) {
 int plan_pixel_bits(mvae_ctx* c, const CreateOpts& opt) {
   GemmDesc& f0 = c->fwd_enc[0];
   GemmDesc& w0 = c->bwd_enc[c->nenc];
-  if (!(opt.bits && c->np && !c->conv && c->xbits && c->B % 64 == 0 && c->x32mask == 0 && plane_kernel(f0) &&
+  if (!(opt.bits && c->np && !c->conv && c->in_dst.xbits && c->B % 64 == 0 && c->x32mask == 0 && plane_kernel(f0) &&
         plane_kernel(w0) && f0.A == c->xs && w0.A == c->xs))
     return MVAE_OK;
-  c->kts_f = bitmat_kts(c->D + 1);
-  c->kts_w = bitmat_kts(3 * c->B);
-  PLAN_ALLOC(c->xbf, bitmat_words(3 * c->B, c->D + 1));
-  PLAN_ALLOC(c->xbw, bitmat_words(c->D + 1, 3 * c->B));
-  f0.Abits = c->xbf; f0.abits_kts = c->kts_f; f0.anb = c->dyn + 2;
+  BitsDst& t = c->in_dst;
+  t.kts_f = bitmat_kts(c->D + 1);
+  t.kts_w = bitmat_kts(3 * c->B);
+  PLAN_ALLOC(t.xbf, bitmat_words(3 * c->B, c->D + 1));
+  PLAN_ALLOC(t.xbw, bitmat_words(c->D + 1, 3 * c->B));
+  f0.Abits = t.xbf; f0.abits_kts = t.kts_f; f0.anb = c->dyn + 2;
   // the weight gradient's batch 2 (g2) reads stacked rows B .. 3B: k-tiles from B / 64
-  w0.Abits = c->xbw; w0.abits_kts = c->kts_w; w0.anb = c->dyn + 2;
+  w0.Abits = t.xbw; w0.abits_kts = t.kts_w; w0.anb = c->dyn + 2;
   w0.abits_sb = (long long)(c->B / 64) * BITMAT_BLOCK_WORDS;
   f0.bits_reg = w0.bits_reg = opt.bits_reg;
   c->bits_on = true;

@@ -8,26 +8,90 @@
 // latent mean/log-sigma heads only (transform: no eps, no z, no column statistics).
 enum { ENC_TRAIN = 0, ENC_EVAL = 1, ENC_MEAN = 2 };
 
-// The batch is x, or (x == NULL) the pairs descriptor. A pairs batch takes the direct kernel
-// (launch_pairs_bits: the BitMats straight from the tables) exactly where an x batch would take the
-// bits branch below and the launcher's shape / alignment conditions hold; in every other
-// configuration X is materialised into the context's scratch and the x code runs on it. kidx (the
-// *_xpairs entry points): the key of each row, NULL for the own pair (pairs->idx).
-//
-// One pass of mvae_embed_images (x and pairs NULL): the 3B images [first, first + 3B) of the call,
-// image t of the pass being stacked row t; it takes its direct kernel (launch_images_bits) under
-// the same conditions, else launch_images_x materialises the pass into the same scratch.
-struct EmbedPass {
-  const mvae_images* im;
-  const int* idx;  // im->idx + first, or NULL
-  const unsigned char* table;  // im->table (idx given) or im->table + first D
-  int nvalid;      // min(3B, count - first)
+// What a pass encodes: the caller's X, a pairs batch (the *_pairs and *_xpairs entry points), or one
+// pass of mvae_embed_images -- the 3B images [first, first + 3B) of the call, image t of the pass
+// being stacked row t.
+struct BatchSrc {
+  enum Kind { X, PAIRS, IMAGES } kind;
+  const float* x;
+  PairsBatch pairs;
+  ImagesBatch images;
 };
-static int encode(mvae_ctx* ctx, const float* x, const float* eps, hipStream_t st, int draw = ENC_TRAIN,
-                  const mvae_pairs* pairs = nullptr, const EmbedPass* ep = nullptr, const int* kidx = nullptr) {
+static BatchSrc batch_x(const float* x) {
+  BatchSrc s{};
+  s.kind = BatchSrc::X;
+  s.x = x;
+  return s;
+}
+// kidx (the *_xpairs entry points): the key of each row, NULL for the own pair (p->idx)
+static BatchSrc batch_pairs(const mvae_ctx* c, const mvae_pairs* p, const int* kidx = nullptr) {
+  BatchSrc s{};
+  s.kind = BatchSrc::PAIRS;
+  s.pairs = PairsBatch{p->locks, p->keys, p->height, p->width, p->idx, kidx, p->coef, p->divisor, c->B};
+  return s;
+}
+
+// The input stage of a pass: the batch into the layer-0 operand (mvae_ctx::in_dst). A pairs batch or
+// an embedding pass takes its direct kernel (launch_pairs_bits / launch_images_bits: the BitMats
+// straight from the tables) exactly where an x batch would take the bits branch below and the
+// launcher's shape / alignment conditions hold; in every other configuration X is materialised into
+// the context's scratch and the x code runs on it. train: the pass feeds a backward (evaluation
+// passes need no xbw).
+static int batch_input(mvae_ctx* ctx, const BatchSrc& src, bool train, hipStream_t st) {
   auto c = ctx;
-  const bool direct = c->bits_on && ((pairs && pairs_bits_fits(pairs->locks, pairs->keys, pairs->coef, c->B, c->D)) ||
-                                     (ep && images_bits_fits(ep->table, c->B, c->D)));
+  const BitsDst& dst = c->in_dst;
+  const PairsBatch& pb = src.pairs;
+  const ImagesBatch& ib = src.images;
+  const bool direct = c->bits_on && ((src.kind == BatchSrc::PAIRS && pairs_bits_fits(pb.locks, pb.keys, pb.coef, c->B, c->D)) ||
+                                     (src.kind == BatchSrc::IMAGES && images_bits_fits(ib.table, c->B, c->D)));
+  const float* x = src.x;
+  if (src.kind != BatchSrc::X && !direct) {
+    if (!c->pairs_x) {
+      void* q = nullptr;
+      MV_CHECK(hipMalloc(&q, (size_t)c->B * 3 * c->D * sizeof(float)));
+      c->allocs.push_back(q);
+      c->pairs_x = static_cast<float*>(q);
+    }
+    if (src.kind == BatchSrc::PAIRS)
+      TIMED_CHECK("pairs_make_batch", launch_make_batch(pb.locks, pb.keys, pb.H, pb.W, pb.idx, pb.kidx, pb.coef, c->B,
+                                                        pb.div, c->pairs_x, st));
+    else
+      TIMED_CHECK("images_make_x", launch_images_x(ib, c->pairs_x, st));
+    x = c->pairs_x;
+  }
+  const char* name = !direct ? "deinterleave" : (src.kind == BatchSrc::IMAGES ? "images_bits" : "pairs_bits");
+  TimeScope ts_deint(ctx, region(ctx, name), st);
+  // the flag's slots alternate: this pass raises the one the previous pass zeroed and zeroes
+  // the previous one (its readers are all behind on this stream), no memset launch per step
+  int* prev = c->dyn_cur ? c->dyn_cur : c->dyn;
+  int* cur = c->dyn ? (prev == c->dyn ? c->dyn + 1 : c->dyn) : nullptr;
+  if (c->bits_on) {  // the BitMats and target bits; the planes only for a batch not all 0 / 1
+    const bool split = c->xbw_split && train;
+    if (direct && src.kind == BatchSrc::IMAGES)  // (an evaluation pass: the forward words only, no transpose)
+      MV_CHECK(launch_images_bits(ib, dst, cur, prev, true, st));
+    else if (direct)
+      MV_CHECK(launch_pairs_bits(pb, dst, cur, prev, split, st));
+    else
+      MV_CHECK(launch_deint_bits(XBatch{x, c->B, c->D}, dst, cur, prev, split, st));
+    if (split) {  // xbw from xbf on the side stream, beside the layer-0 forward
+      const bool two = c->use_side && c->side;
+      hipStream_t sd = two ? c->side : st;
+      if (two)
+        if (int rc = stream_wait(c, st, sd)) return rc;
+      MV_CHECK(launch_bits_transpose(dst.xbf, dst.kts_f, dst.xbw, dst.kts_w, c->B, sd));
+      MV_CHECK(hipEventRecord(c->xbw_ev, sd));
+      c->xbw_pending = true;
+    }
+  } else {
+    MV_CHECK(launch_deinterleave(x, dst.xs, dst.xp, cur, c->dyn ? prev : nullptr, c->B, c->D, dst.ldx, c->x32mask,
+                                 dst.f32dyn_mask, st, dst.xbits, dst.ldbits));
+  }
+  c->dyn_cur = cur;
+  return MVAE_OK;
+}
+
+static int encode(mvae_ctx* ctx, const BatchSrc& src, const float* eps, hipStream_t st, int draw = ENC_TRAIN) {
+  auto c = ctx;
   if (c->side && c->side_pending) {  // an early-Adam backward whose mvae_adam never came
     c->side_pending = false;
     c->early_fork = false;
@@ -37,55 +101,7 @@ static int encode(mvae_ctx* ctx, const float* x, const float* eps, hipStream_t s
     c->xbw_pending = false;
     MV_CHECK(hipStreamWaitEvent(st, c->xbw_ev, 0));
   }
-  if ((pairs || ep) && !direct) {
-    if (!c->pairs_x) {
-      void* q = nullptr;
-      MV_CHECK(hipMalloc(&q, (size_t)c->B * 3 * c->D * sizeof(float)));
-      c->allocs.push_back(q);
-      c->pairs_x = static_cast<float*>(q);
-    }
-    if (pairs)
-      TIMED_CHECK("pairs_make_batch", launch_make_batch(pairs->locks, pairs->keys, pairs->height, pairs->width, pairs->idx,
-                                                        kidx, pairs->coef, c->B, pairs->divisor, c->pairs_x, st));
-    else
-      TIMED_CHECK("images_make_x", launch_images_x(ep->table, ep->im->height, ep->im->width, ep->idx, ep->nvalid,
-                                                   ep->im->divisor, c->B, c->pairs_x, st));
-    x = c->pairs_x;
-  }
-  {
-    TimeScope ts_deint(ctx, region(ctx, direct ? (ep ? "images_bits" : "pairs_bits") : "deinterleave"), st);
-    // the flag's slots alternate: this pass raises the one the previous pass zeroed and zeroes
-    // the previous one (its readers are all behind on this stream), no memset launch per step
-    int* prev = c->dyn_cur ? c->dyn_cur : c->dyn;
-    int* cur = c->dyn ? (prev == c->dyn ? c->dyn + 1 : c->dyn) : nullptr;
-    if (c->bits_on) {  // the BitMats and target bits; the planes only for a batch not all 0 / 1
-      const bool split = c->xbw_split && draw == ENC_TRAIN;  // (eval passes need no xbw)
-      if (direct && ep)  // (an evaluation pass: the forward words only, no transpose)
-        MV_CHECK(launch_images_bits(ep->table, ep->im->height, ep->im->width, ep->idx, ep->nvalid, ep->im->divisor,
-                                    c->B, c->xbf, c->kts_f, c->xbw, c->kts_w, c->xbits, c->ldbits, cur, prev, c->xs,
-                                    planes_of(c, c->xs), c->ldx, c->x32dyn, true, st));
-      else if (direct)
-        MV_CHECK(launch_pairs_bits(pairs->locks, pairs->keys, pairs->height, pairs->width, pairs->idx, kidx,
-                                   pairs->coef, pairs->divisor, c->B, c->xbf, c->kts_f, c->xbw, c->kts_w, c->xbits, c->ldbits,
-                                   cur, prev, c->xs, planes_of(c, c->xs), c->ldx, c->x32dyn, split, st));
-      else
-        MV_CHECK(launch_deint_bits(x, c->B, c->D, c->xbf, c->kts_f, c->xbw, c->kts_w, c->xbits, c->ldbits, cur,
-                                   prev, c->xs, planes_of(c, c->xs), c->ldx, c->x32dyn, split, st));
-      if (split) {  // xbw from xbf on the side stream, beside the layer-0 forward
-        const bool two = c->use_side && c->side;
-        hipStream_t sd = two ? c->side : st;
-        if (two)
-          if (int rc = stream_wait(c, st, sd)) return rc;
-        MV_CHECK(launch_bits_transpose(c->xbf, c->kts_f, c->xbw, c->kts_w, c->B, sd));
-        MV_CHECK(hipEventRecord(c->xbw_ev, sd));
-        c->xbw_pending = true;
-      }
-    }
-    else
-      MV_CHECK(launch_deinterleave(x, c->xs, planes_of(c, c->xs), cur, c->dyn ? prev : nullptr, c->B,
-                                   c->D, c->ldx, c->x32mask, c->x32dyn, st, c->xbits, c->ldbits));
-    c->dyn_cur = cur;
-  }
+  if (int rc = batch_input(ctx, src, draw == ENC_TRAIN, st)) return rc;
   const size_t ne = (size_t)3 * c->B * c->L;
   if (draw != ENC_MEAN) {
     // eps of this forward: the caller's draws (copied: the backward needs them after the
@@ -161,10 +177,9 @@ static int check_pairs(mvae_ctx* ctx, const mvae_pairs* p, const char* who) {
   return MVAE_OK;
 }
 
-static int forward_any(mvae_ctx* ctx, const float* x, const mvae_pairs* pairs, const float* eps, void* stream,
-                       const int* kidx = nullptr) {
+static int forward_any(mvae_ctx* ctx, const BatchSrc& src, const float* eps, void* stream) {
   hipStream_t st = (hipStream_t)stream;
-  int rc = encode(ctx, x, eps, st, ENC_TRAIN, pairs, nullptr, kidx);
+  int rc = encode(ctx, src, eps, st, ENC_TRAIN);
   if (rc) return rc;
   if ((rc = decode_hidden(ctx, st))) return rc;
   if (ctx->f_split && ctx->use_split) {
@@ -179,13 +194,13 @@ static int forward_any(mvae_ctx* ctx, const float* x, const mvae_pairs* pairs, c
 
 extern "C" int mvae_forward(mvae_ctx* ctx, const float* x, const float* eps, void* stream) {
   if (!ctx || !x) return MVAE_EINVAL;
-  return forward_any(ctx, x, nullptr, eps, stream);
+  return forward_any(ctx, batch_x(x), eps, stream);
 }
 
 extern "C" int mvae_forward_pairs(mvae_ctx* ctx, const mvae_pairs* pairs, const float* eps, void* stream) {
   if (!ctx) return MVAE_EINVAL;
   if (int rc = check_pairs(ctx, pairs, "mvae_forward_pairs")) return rc;
-  return forward_any(ctx, nullptr, pairs, eps, stream);
+  return forward_any(ctx, batch_pairs(ctx, pairs), eps, stream);
 }
 
 // the *_xpairs twins: the *_pairs code with the key of each row from key_idx
@@ -196,7 +211,7 @@ static int check_xpairs(mvae_ctx* ctx, const mvae_xpairs* xp, const char* who) {
 extern "C" int mvae_forward_xpairs(mvae_ctx* ctx, const mvae_xpairs* xp, const float* eps, void* stream) {
   if (!ctx) return MVAE_EINVAL;
   if (int rc = check_xpairs(ctx, xp, "mvae_forward_xpairs")) return rc;
-  return forward_any(ctx, nullptr, &xp->p, eps, stream, xp->key_idx);
+  return forward_any(ctx, batch_pairs(ctx, &xp->p, xp->key_idx), eps, stream);
 }
 
 extern "C" int mvae_metric(mvae_ctx* ctx, const float* areas, void* stream) {
@@ -405,11 +420,10 @@ extern "C" int mvae_adam(mvae_ctx* ctx, void* stream) {
   return MVAE_OK;
 }
 
-static int train_step_any(mvae_ctx* ctx, const float* x, const mvae_pairs* pairs, const float* areas,
-                          const float* eps, float* losses_out, float* dist_out, void* stream,
-                          const int* kidx = nullptr) {
+static int train_step_any(mvae_ctx* ctx, const BatchSrc& src, const float* areas, const float* eps,
+                          float* losses_out, float* dist_out, void* stream) {
   int rc;
-  if ((rc = forward_any(ctx, x, pairs, eps, stream, kidx))) return rc;
+  if ((rc = forward_any(ctx, src, eps, stream))) return rc;
   if ((rc = mvae_metric(ctx, areas, stream))) return rc;
   hipStream_t st = (hipStream_t)stream;
   if (losses_out) MV_CHECK(hipMemcpyAsync(losses_out, ctx->losses, 5 * sizeof(float), hipMemcpyDeviceToDevice, st));
@@ -428,28 +442,27 @@ static int train_step_any(mvae_ctx* ctx, const float* x, const mvae_pairs* pairs
 extern "C" int mvae_train_step(mvae_ctx* ctx, const float* x, const float* areas, const float* eps,
                                float* losses_out, float* dist_out, void* stream) {
   if (!ctx || !x || !areas) return MVAE_EINVAL;
-  return train_step_any(ctx, x, nullptr, areas, eps, losses_out, dist_out, stream);
+  return train_step_any(ctx, batch_x(x), areas, eps, losses_out, dist_out, stream);
 }
 
 extern "C" int mvae_train_step_pairs(mvae_ctx* ctx, const mvae_pairs* pairs, const float* areas, const float* eps,
                                      float* losses_out, float* dist_out, void* stream) {
   if (!ctx || !areas) return MVAE_EINVAL;
   if (int rc = check_pairs(ctx, pairs, "mvae_train_step_pairs")) return rc;
-  return train_step_any(ctx, nullptr, pairs, areas, eps, losses_out, dist_out, stream);
+  return train_step_any(ctx, batch_pairs(ctx, pairs), areas, eps, losses_out, dist_out, stream);
 }
 
 extern "C" int mvae_train_step_xpairs(mvae_ctx* ctx, const mvae_xpairs* xp, const float* areas, const float* eps,
                                       float* losses_out, float* dist_out, void* stream) {
   if (!ctx || !areas) return MVAE_EINVAL;
   if (int rc = check_xpairs(ctx, xp, "mvae_train_step_xpairs")) return rc;
-  return train_step_any(ctx, nullptr, &xp->p, areas, eps, losses_out, dist_out, stream, xp->key_idx);
+  return train_step_any(ctx, batch_pairs(ctx, &xp->p, xp->key_idx), areas, eps, losses_out, dist_out, stream);
 }
 
 // get_predictions in two phases (a data-parallel host all-reduces MVAE_BUF_COLSQ between them:
 // the cosine distance normalises over the GLOBAL batch, 8c/vae.py:449-450)
-static int predict_encode_any(mvae_ctx* ctx, const float* x, const mvae_pairs* pairs, const float* eps,
-                              void* stream, const int* kidx = nullptr) {
-  int rc = encode(ctx, x, eps, (hipStream_t)stream, ENC_EVAL, pairs, nullptr, kidx);
+static int predict_encode_any(mvae_ctx* ctx, const BatchSrc& src, const float* eps, void* stream) {
+  int rc = encode(ctx, src, eps, (hipStream_t)stream, ENC_EVAL);
   if (rc) return rc;
   ctx->phase = 6;
   return MVAE_OK;
@@ -457,19 +470,19 @@ static int predict_encode_any(mvae_ctx* ctx, const float* x, const mvae_pairs* p
 
 extern "C" int mvae_predict_encode(mvae_ctx* ctx, const float* x, const float* eps, void* stream) {
   if (!ctx || !x) return MVAE_EINVAL;
-  return predict_encode_any(ctx, x, nullptr, eps, stream);
+  return predict_encode_any(ctx, batch_x(x), eps, stream);
 }
 
 extern "C" int mvae_predict_encode_pairs(mvae_ctx* ctx, const mvae_pairs* pairs, const float* eps, void* stream) {
   if (!ctx) return MVAE_EINVAL;
   if (int rc = check_pairs(ctx, pairs, "mvae_predict_encode_pairs")) return rc;
-  return predict_encode_any(ctx, nullptr, pairs, eps, stream);
+  return predict_encode_any(ctx, batch_pairs(ctx, pairs), eps, stream);
 }
 
 extern "C" int mvae_predict_encode_xpairs(mvae_ctx* ctx, const mvae_xpairs* xp, const float* eps, void* stream) {
   if (!ctx) return MVAE_EINVAL;
   if (int rc = check_xpairs(ctx, xp, "mvae_predict_encode_xpairs")) return rc;
-  return predict_encode_any(ctx, nullptr, &xp->p, eps, stream, xp->key_idx);
+  return predict_encode_any(ctx, batch_pairs(ctx, &xp->p, xp->key_idx), eps, stream);
 }
 
 extern "C" int mvae_predict_finish(mvae_ctx* ctx, float* dist_out, void* stream) {
@@ -501,14 +514,13 @@ extern "C" int mvae_predict_xpairs(mvae_ctx* ctx, const mvae_xpairs* xp, const f
                                    void* stream) {
   if (!ctx || !dist_out) return MVAE_EINVAL;
   if (int rc = check_xpairs(ctx, xp, "mvae_predict_xpairs")) return rc;
-  int rc = predict_encode_any(ctx, nullptr, &xp->p, eps, stream, xp->key_idx);
+  int rc = predict_encode_any(ctx, batch_pairs(ctx, &xp->p, xp->key_idx), eps, stream);
   return rc ? rc : mvae_predict_finish(ctx, dist_out, stream);
 }
 
-static int transform_any(mvae_ctx* ctx, const float* x, const mvae_pairs* pairs, float* zmean_out, void* stream,
-                         const int* kidx = nullptr) {
+static int transform_any(mvae_ctx* ctx, const BatchSrc& src, float* zmean_out, void* stream) {
   hipStream_t st = (hipStream_t)stream;
-  int rc = encode(ctx, x, nullptr, st, ENC_MEAN, pairs, nullptr, kidx);
+  int rc = encode(ctx, src, nullptr, st, ENC_MEAN);
   if (rc) return rc;
   MV_CHECK(launch_copy2d(ctx->ms + (size_t)ctx->B * 2 * ctx->L, 2 * ctx->L, zmean_out, ctx->L,
                          ctx->B, ctx->L, st));
@@ -518,19 +530,19 @@ static int transform_any(mvae_ctx* ctx, const float* x, const mvae_pairs* pairs,
 
 extern "C" int mvae_transform(mvae_ctx* ctx, const float* x, float* zmean_out, void* stream) {
   if (!ctx || !x || !zmean_out) return MVAE_EINVAL;
-  return transform_any(ctx, x, nullptr, zmean_out, stream);
+  return transform_any(ctx, batch_x(x), zmean_out, stream);
 }
 
 extern "C" int mvae_transform_pairs(mvae_ctx* ctx, const mvae_pairs* pairs, float* zmean_out, void* stream) {
   if (!ctx || !zmean_out) return MVAE_EINVAL;
   if (int rc = check_pairs(ctx, pairs, "mvae_transform_pairs")) return rc;
-  return transform_any(ctx, nullptr, pairs, zmean_out, stream);
+  return transform_any(ctx, batch_pairs(ctx, pairs), zmean_out, stream);
 }
 
 extern "C" int mvae_transform_xpairs(mvae_ctx* ctx, const mvae_xpairs* xp, float* zmean_out, void* stream) {
   if (!ctx || !zmean_out) return MVAE_EINVAL;
   if (int rc = check_xpairs(ctx, xp, "mvae_transform_xpairs")) return rc;
-  return transform_any(ctx, nullptr, &xp->p, zmean_out, stream, xp->key_idx);
+  return transform_any(ctx, batch_pairs(ctx, &xp->p, xp->key_idx), zmean_out, stream);
 }
 
 // ceil(count / 3B) encoder passes, every stacked row a wanted image; the means (and log-sigmas) of
@@ -550,24 +562,24 @@ extern "C" int mvae_embed_images(mvae_ctx* ctx, const mvae_images* im, int64_t c
   const int64_t rows = 3 * (int64_t)ctx->B;
   const int L = ctx->L;
   for (int64_t first = 0; first < count; first += rows) {
-    EmbedPass ep;
-    ep.im = im;
-    ep.idx = im->idx ? im->idx + first : nullptr;
-    ep.table = im->idx ? im->table : im->table + (size_t)first * ctx->D;
-    ep.nvalid = (int)std::min<int64_t>(rows, count - first);
-    int rc = encode(ctx, nullptr, nullptr, st, ENC_MEAN, nullptr, &ep);
+    BatchSrc pass{};
+    pass.kind = BatchSrc::IMAGES;
+    const int nvalid = (int)std::min<int64_t>(rows, count - first);
+    // (idx given: the whole table and this pass's indices; else the table from image `first` on)
+    pass.images = ImagesBatch{im->idx ? im->table : im->table + (size_t)first * ctx->D, im->height, im->width,
+                              im->idx ? im->idx + first : nullptr, nvalid, im->divisor, ctx->B};
+    int rc = encode(ctx, pass, nullptr, st, ENC_MEAN);
     if (rc) return rc;
     TIMED("embed_copy_out");
-    MV_CHECK(launch_copy2d(ctx->ms, 2 * L, zmean_out + (size_t)first * L, L, ep.nvalid, L, st));
-    if (zlogsig_out) MV_CHECK(launch_copy2d(ctx->ms + L, 2 * L, zlogsig_out + (size_t)first * L, L, ep.nvalid, L, st));
+    MV_CHECK(launch_copy2d(ctx->ms, 2 * L, zmean_out + (size_t)first * L, L, nvalid, L, st));
+    if (zlogsig_out) MV_CHECK(launch_copy2d(ctx->ms + L, 2 * L, zlogsig_out + (size_t)first * L, L, nvalid, L, st));
   }
   ctx->phase = 0;
   return MVAE_OK;
 }
-static int reconstruct_any(mvae_ctx* ctx, const float* x, const mvae_pairs* pairs, const float* eps, float* y_out,
-                           void* stream, const int* kidx = nullptr) {
+static int reconstruct_any(mvae_ctx* ctx, const BatchSrc& src, const float* eps, float* y_out, void* stream) {
   hipStream_t st = (hipStream_t)stream;
-  int rc = encode(ctx, x, eps, st, ENC_EVAL, pairs, nullptr, kidx);
+  int rc = encode(ctx, src, eps, st, ENC_EVAL);
   if (rc) return rc;
   if ((rc = decode_hidden(ctx, st))) return rc;
   GemmDesc d = ctx->f_out;
@@ -580,21 +592,21 @@ static int reconstruct_any(mvae_ctx* ctx, const float* x, const mvae_pairs* pair
 
 extern "C" int mvae_reconstruct(mvae_ctx* ctx, const float* x, const float* eps, float* y_out, void* stream) {
   if (!ctx || !x || !y_out) return MVAE_EINVAL;
-  return reconstruct_any(ctx, x, nullptr, eps, y_out, stream);
+  return reconstruct_any(ctx, batch_x(x), eps, y_out, stream);
 }
 
 extern "C" int mvae_reconstruct_pairs(mvae_ctx* ctx, const mvae_pairs* pairs, const float* eps, float* y_out,
                                       void* stream) {
   if (!ctx || !y_out) return MVAE_EINVAL;
   if (int rc = check_pairs(ctx, pairs, "mvae_reconstruct_pairs")) return rc;
-  return reconstruct_any(ctx, nullptr, pairs, eps, y_out, stream);
+  return reconstruct_any(ctx, batch_pairs(ctx, pairs), eps, y_out, stream);
 }
 
 extern "C" int mvae_reconstruct_xpairs(mvae_ctx* ctx, const mvae_xpairs* xp, const float* eps, float* y_out,
                                        void* stream) {
   if (!ctx || !y_out) return MVAE_EINVAL;
   if (int rc = check_xpairs(ctx, xp, "mvae_reconstruct_xpairs")) return rc;
-  return reconstruct_any(ctx, nullptr, &xp->p, eps, y_out, stream, xp->key_idx);
+  return reconstruct_any(ctx, batch_pairs(ctx, &xp->p, xp->key_idx), eps, y_out, stream);
 }
 
 extern "C" int mvae_generate(mvae_ctx* ctx, const float* zin, int n, float* y_out, void* stream) {

@@ -2,7 +2,7 @@
 // the quantity the model's latent distance is trained to predict, computed from the uint8 tables.
 //   Lb, Kb      foreground = table byte >= 128
 //   Kr_r        the key rotated by coef[r] = (cos, sin, x_off, y_off) with make_batch_kernel's
-//               arithmetic (mvae_kernels.hip: output (x, y) samples ((c x - s y) + x_off,
+//               arithmetic (batch_input.hip rot_sample: output (x, y) samples ((c x - s y) + x_off,
 //               (s x + c y) + y_off), unfused fp32, roundf, zero fill), bit for bit
 //   ov(r, dy, dx) = sum_{y,x} Lb[y, x] Kr_r[y - dy, x - dx],  |dy| <= H - 1, |dx| <= W - 1
 //   area = max ov;  pose = the lexicographically smallest (r, dy, dx) reaching it; (0, 0, 0) when

@@ -760,6 +760,42 @@ typedef struct mvae_plan_out {
   unsigned long long ws_elems;
 } mvae_plan_out;
 int mvae_debug_plan(const mvae_plan_args* args, mvae_plan_out* out);
+/* One batched GEMM on caller data, through gemm_run (tests; synchronous; additive to ABI 7): what
+ * mvae_debug_gemm does, with the dimensions it fixes -- the batch and its strides, a forced split-K,
+ * the tile order, the operand images' alignment. A, B, C are fp32 device buffers of a_elems, b_elems,
+ * c_elems elements; element b of the batch reads A + b sA ([M][lda], or [K][lda] with at), B + b sB
+ * ([K][ldb], or [N][ldb] with bt) and writes C + b sC ([M][ldc]). The bf16 planes of the plane modes
+ * are split here over the whole A and B buffers (so the batch windows of A and of B may overlap) and
+ * start a_off / b_off elements (0..7) past a 16-byte boundary; the split-K workspace is allocated
+ * here and filled with NaN bits before the launch. A zeroed field is its default.
+ *  prec 0 fp32, 1 bf16, 2 f32x; variant: a kernel number (mvae_debug_plan's table); x3: the
+ *  plane-stacked kernel where it serves; tm 0 / 192 / 256: the ring tile's rows; split 0: the planner's.
+ *  group: the tile order of the 256-row kernels -- 0 the planner's, g > 0 bands of g m-tiles, -1 row by row.
+ *  epi 0 store, 1 act (act 0 tanh, 1 elu).
+ *  bits 1 / 2 (plane modes, A of 0/1 values): A also as a BitMat, read by the eight-phase kernel through
+ *  LDS / into registers. bits_shared 0: one BitMat of M x K per batch element. bits_shared 1 (at = 1, sA
+ *  a multiple of 64 lda): one BitMat of the whole stored A, element b at k-tile b sA / (64 lda) of every
+ *  strip -- the form of the step's layer-0 weight gradient.
+ * *plan (or NULL) receives the plan gemm_run launched.
+ * MVAE_EINVAL with a message, before any HIP call: args or a buffer NULL, a size < 1, a stride smaller
+ * than its row, a negative batch stride, an extent smaller than (batch - 1) s + rows ld, output
+ * windows that overlap (batch > 1 and sC < (M - 1) ldc + N), prec / variant / x3 / tm / epi / act /
+ * bits / group / an offset out of range, split < 0, bits in fp32 (prec 0 or variant 9), bits_shared
+ * without bits, at = 1 and sA a multiple of 64 lda. */
+typedef struct mvae_gemm_args {
+  int M, N, K, batch, at, bt;
+  int lda, ldb, ldc;
+  int prec, variant, x3, tm, split, group;
+  int epi, act;
+  int bits, bits_shared;
+  int a_off, b_off;
+  long long sA, sB, sC;             /* batch strides, elements */
+  long long a_elems, b_elems, c_elems;
+  const float* A;
+  const float* B;
+  float* C;
+} mvae_gemm_args;
+int mvae_debug_gemm_ex(const mvae_gemm_args* args, mvae_plan_out* plan, void* stream);
 
 #ifdef __cplusplus
 }

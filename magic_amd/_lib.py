@@ -121,6 +121,16 @@ class mvae_plan_out(C.Structure):
                 [("ws_elems", C.c_ulonglong)])
 
 
+class mvae_gemm_args(C.Structure):
+    """Arguments of ``mvae_debug_gemm_ex`` (``include/mvae.h``): one batched GEMM on caller buffers; a
+    zeroed field is its default."""
+    _fields_ = ([(n, C.c_int) for n in ("M", "N", "K", "batch", "at", "bt", "lda", "ldb", "ldc", "prec", "variant",
+                                        "x3", "tm", "split", "group", "epi", "act", "bits", "bits_shared", "a_off",
+                                        "b_off")] +
+                [(n, C.c_longlong) for n in ("sA", "sB", "sC", "a_elems", "b_elems", "c_elems")] +
+                [(n, C.c_void_p) for n in ("A", "B", "C")])
+
+
 KERNEL_NAMES = {1: "f32", 2: "valu", 3: "plane", 4: "ring", 5: "x3", 6: "e8"}
 
 
@@ -231,6 +241,7 @@ _SIGS = {
     "mvae_debug_head": ([C.POINTER(mvae_head_args), C.c_void_p], C.c_int),
     "mvae_debug_epi": ([C.POINTER(mvae_epi_args), C.c_void_p], C.c_int),
     "mvae_debug_plan": ([C.POINTER(mvae_plan_args), C.POINTER(mvae_plan_out)], C.c_int),
+    "mvae_debug_gemm_ex": ([C.POINTER(mvae_gemm_args), C.POINTER(mvae_plan_out), C.c_void_p], C.c_int),
 }
 
 EXPORTED = tuple(_SIGS)

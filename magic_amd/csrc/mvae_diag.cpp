@@ -862,3 +862,104 @@ extern "C" int mvae_debug_plan(const mvae_plan_args* args, mvae_plan_out* out) {
                        (int)gemm_plan_refused(pl, ws, (size_t)a.max_ws), pl.ws_elems};
   return MVAE_OK;
 }
+
+// One batched GEMM on caller buffers (tests only; synchronous): the GemmDesc mvae_debug_gemm builds,
+// with what that entry fixes at one value -- the batch and its strides, a forced split, the tile
+// order, the plane images' alignment, the BitMat's two batch forms. Everything the kernels'
+// addressing relies on is checked here, before any HIP call; include/mvae.h lists the fields.
+extern "C" int mvae_debug_gemm_ex(const mvae_gemm_args* args, mvae_plan_out* plan, void* stream) {
+  const char* who = "mvae_debug_gemm_ex: ";
+  auto bad = [&](const std::string& m) { return fail(nullptr, MVAE_EINVAL, who + m); };
+  if (!args) return bad("args is NULL");
+  const mvae_gemm_args& a = *args;
+  if (!a.A || !a.B || !a.C) return bad("A, B or C is NULL");
+  if (a.M < 1 || a.N < 1 || a.K < 1 || a.batch < 1) return bad("M, N, K and batch must be at least 1");
+  if (a.M > (1 << 24) || a.N > (1 << 24) || a.K > (1 << 24) || a.batch > (1 << 16)) return bad("M, N, K or batch too large");
+  if ((a.at != 0 && a.at != 1) || (a.bt != 0 && a.bt != 1)) return bad("at and bt must be 0 or 1");
+  if (a.prec < GEMM_F32 || a.prec > GEMM_F32X) return bad("prec must be 0, 1 or 2");
+  if (a.variant < 0 || a.variant > 15) return bad("variant must be in [0, 15]");
+  if (a.x3 < 0 || a.x3 > 2) return bad("x3 must be in [0, 2]");
+  if (a.tm != 0 && a.tm != 192 && a.tm != 256) return bad("tm must be 0, 192 or 256");
+  if (a.split < 0 || a.split > 64) return bad("split must be in [0, 64]");
+  if (a.group < -1 || a.group > (1 << 16)) return bad("group must be -1, 0 or a band height");
+  if (a.epi != EPI_STORE && a.epi != EPI_ACT) return bad("epi must be 0 (store) or 1 (act)");
+  if (a.act != ACT_TANH && a.act != ACT_ELU) return bad("act must be 0 (tanh) or 1 (elu)");
+  if (a.bits < 0 || a.bits > 2) return bad("bits must be 0, 1 or 2");
+  if (a.a_off < 0 || a.a_off > 7 || a.b_off < 0 || a.b_off > 7) return bad("a_off and b_off must be in [0, 7]");
+  const int arows = a.at ? a.K : a.M, acols = a.at ? a.M : a.K;
+  const int brows = a.bt ? a.N : a.K, bcols = a.bt ? a.K : a.N;
+  if (a.lda < acols) return bad("lda is smaller than a row");
+  if (a.ldb < bcols) return bad("ldb is smaller than a row");
+  if (a.ldc < a.N) return bad("ldc is smaller than a row");
+  if (a.sA < 0 || a.sB < 0 || a.sC < 0) return bad("a batch stride is negative");
+  if (a.sA > (1LL << 40) || a.sB > (1LL << 40) || a.sC > (1LL << 40)) return bad("a batch stride is too large");
+  const long long nb1 = a.batch - 1;
+  if (a.a_elems < nb1 * a.sA + (long long)arows * a.lda) return bad("a_elems is smaller than the batch's A windows");
+  if (a.b_elems < nb1 * a.sB + (long long)brows * a.ldb) return bad("b_elems is smaller than the batch's B windows");
+  if (a.c_elems < nb1 * a.sC + (long long)a.M * a.ldc) return bad("c_elems is smaller than the batch's C windows");
+  if (a.batch > 1 && a.sC < (long long)(a.M - 1) * a.ldc + a.N) return bad("the output windows overlap");
+  const bool fp32 = a.prec == GEMM_F32 || a.variant == 9;  // (9: the VALU kernel, fp32 arithmetic)
+  if (a.bits && fp32) return bad("bits needs a plane mode");
+  if (a.bits_shared != 0 && a.bits_shared != 1) return bad("bits_shared must be 0 or 1");
+  if (a.bits_shared && (!a.bits || !a.at || a.sA % (64LL * a.lda)))
+    return bad("bits_shared needs bits, at = 1 and sA a multiple of 64 lda");
+  hipStream_t st = (hipStream_t)stream;
+  Arena ar(st);
+  GemmDesc d = gd(a.M, a.N, a.K, a.A, a.lda, a.at != 0, a.B, a.ldb, a.bt != 0, a.C, a.ldc, a.epi);
+  d.batch = a.batch; d.sA = a.sA; d.sB = a.sB; d.sC = a.sC;
+  d.prec = a.prec;
+  if (!force_desc(a.variant, &d)) return bad("no such kernel number");
+  d.force.tile_m = a.tm;
+  d.force.split = a.split;
+  d.group = a.group == 0 ? -1 : (a.group < 0 ? 0 : a.group);  // (GemmDesc: -1 the planner's, 0 row by row)
+  d.x3 = a.x3;
+  d.epi.act = a.act;
+  if (d.prec != GEMM_F32) {  // plane images of the whole buffers, a_off / b_off past a 16-byte boundary
+    const int np = d.prec == GEMM_BF16 ? 1 : 3;
+    const size_t na = (size_t)a.a_elems, nb = (size_t)a.b_elems;
+    const size_t pa = (na + 7) & ~(size_t)7, pb = (nb + 7) & ~(size_t)7;  // plane strides: multiples of 8
+    auto* ap = ar.alloc<unsigned short>(np * pa + 8);
+    auto* bp = ar.alloc<unsigned short>(np * pb + 8);
+    DIAG(ar.err);
+    Planes A_{ap + a.a_off, (long long)pa, np}, B_{bp + a.b_off, (long long)pb, np};
+    DIAG(launch_split_planes(a.A, na, A_, st));
+    DIAG(launch_split_planes(a.B, nb, B_, st));
+    d.Ap = A_.p; d.pA = A_.stride; d.nA = np;
+    d.Bp = B_.p; d.pB = B_.stride; d.nB = np;
+  }
+  if (a.bits) {  // A (0/1 values) also as a BitMat: one per batch element, or one of the whole stored A
+    auto* pnb = ar.alloc<int>(4, true);
+    if (a.bits_shared) {
+      const long long rs = a.sA / a.lda;  // stored rows (k) between two batch elements
+      const int kall = (int)(nb1 * rs) + a.K, kts = bitmat_kts(kall);
+      auto* pbits = ar.alloc<unsigned>(bitmat_words(a.M, kall));
+      DIAG(ar.err);
+      DIAG(launch_bits_from_plane(d.Ap, a.lda, true, a.M, kall, pbits, kts, pnb, st));
+      d.Abits = pbits; d.abits_kts = kts; d.abits_sb = rs / 64 * BITMAT_BLOCK_WORDS;
+    } else {
+      const int kts = bitmat_kts(a.K);
+      const size_t bw = bitmat_words(a.M, a.K);
+      auto* pbits = ar.alloc<unsigned>(bw * a.batch);
+      DIAG(ar.err);
+      for (int b = 0; b < a.batch; ++b)
+        DIAG(launch_bits_from_plane(d.Ap + (size_t)b * a.sA, a.lda, a.at != 0, a.M, a.K, pbits + b * bw, kts, pnb, st));
+      d.Abits = pbits; d.abits_kts = kts; d.abits_sb = (long long)bw;
+    }
+    d.anb = pnb;
+    d.bits_reg = a.bits == 2;
+  }
+  const size_t ws_n = gemm_workspace_elems(d);
+  float* ws = ws_n ? ar.alloc<float>(ws_n) : nullptr;
+  DIAG(ar.err);
+  // every slice writes its whole slab, an empty one zeros: a slab left unwritten sums to NaN
+  if (ws) DIAG(hipMemsetAsync(ws, 0xff, ws_n * sizeof(float), st));
+  DIAG(gemm_run(d, ws, ws_n, st));
+  DIAG(hipStreamSynchronize(st));
+  if (plan) {
+    const GemmPlan pl = gemm_plan(d, ws ? ws_n : 0, !misaligned(ws));  // (gemm_run's own call)
+    *plan = mvae_plan_out{pl.kernel, pl.staging, pl.tm, pl.tn, pl.ntm, pl.ntn, pl.group, pl.split, pl.kchunk,
+                          (int)pl.lds_epilogue, (int)pl.vec_epilogue, pl.epi_launched, (int)gemm_valu_fits(d),
+                          (int)gemm_plan_refused(pl, ws != nullptr, ws_n), pl.ws_elems};
+  }
+  return MVAE_OK;
+}

@@ -101,3 +101,12 @@ def test_plan_invariants(plans):
     assert (c["epi"][p["epi_launched"] == BCEB] == BCE).all() and (c["epi"][p["epi_launched"] == DACTB] == DACT).all()
     assert (p["vec_epilogue"] <= p["lds_epilogue"]).all()
     assert (p["valu_fits"][c["variant"] != 0] == 0).all()
+
+
+def test_the_recorded_plans_hold_empty_slices(plans):
+    """kchunk is a whole number of k-tiles, so kchunk * split may pass K by whole slices: the planner's own
+    splits (nothing forced) include plans whose last slices start at or past K. The kernels write a zero
+    slab there (tests/test_gpu_gemm_batch.py); DESIGN.md 5t."""
+    c, _, p, _ = plans
+    empty = (p["split"] > 1) & ((p["split"] - 1) * p["kchunk"] >= c["K"])
+    assert (empty & (c["split"] == 0)).any()

@@ -776,12 +776,15 @@ int mvae_debug_plan(const mvae_plan_args* args, mvae_plan_out* out);
  *  LDS / into registers. bits_shared 0: one BitMat of M x K per batch element. bits_shared 1 (at = 1, sA
  *  a multiple of 64 lda): one BitMat of the whole stored A, element b at k-tile b sA / (64 lda) of every
  *  strip -- the form of the step's layer-0 weight gradient.
+ *  a_dyn (prec 2 only): A's run-time flag, the de-interleave's inexact word (GemmDesc::dynA) -- 0 none
+ *  (every plane pair runs), 1 a device word holding 0 (the kernels run only the leading pairs with A's
+ *  plane 0, as the step does for a batch of bf16 values), 2 a word holding 1.
  * *plan (or NULL) receives the plan gemm_run launched.
  * MVAE_EINVAL with a message, before any HIP call: args or a buffer NULL, a size < 1, a stride smaller
  * than its row, a negative batch stride, an extent smaller than (batch - 1) s + rows ld, output
  * windows that overlap (batch > 1 and sC < (M - 1) ldc + N), prec / variant / x3 / tm / epi / act /
  * bits / group / an offset out of range, split < 0, bits in fp32 (prec 0 or variant 9), bits_shared
- * without bits, at = 1 and sA a multiple of 64 lda. */
+ * without bits, at = 1 and sA a multiple of 64 lda, a_dyn outside 0..2 or with prec != 2. */
 typedef struct mvae_gemm_args {
   int M, N, K, batch, at, bt;
   int lda, ldb, ldc;
@@ -794,8 +797,53 @@ typedef struct mvae_gemm_args {
   const float* A;
   const float* B;
   float* C;
+  int a_dyn;                        /* f32x: A's run-time flag (GemmDesc::dynA); 0 none, 1 a word of 0, 2 of 1 */
 } mvae_gemm_args;
 int mvae_debug_gemm_ex(const mvae_gemm_args* args, mvae_plan_out* plan, void* stream);
+/* The plane side of batch input on caller data, through one of the step's launchers (tests;
+ * synchronous; allocates nothing; additive to ABI 7). Every pointer is a device pointer; a buffer the
+ * route does not name is not read (it may be NULL). A batch of B rows of H x W images, D = H W; the
+ * stacked rows are [rot | lock | key], 3B rows of ldx elements.
+ *  route 0  launch_deinterleave (the plane path) on x [B][3D] fp32: the alignment of x, D and ldx choose
+ *           the 8-pixel, 4-pixel or scalar form; any D >= 1
+ *  route 1  launch_deint_bits on x
+ *  route 2  launch_pairs_bits on the uint8 tables locks, keys with idx [B], key_idx [B] (NULL: idx),
+ *           coef [B][4] and divisor
+ *  route 3  launch_images_bits on the one table in locks with idx [3B] and divisor
+ * np (0, 1 or 3): the bf16 planes written into planes [np][plane_stride]; 0 (route 0 only): no plane
+ * image, the fp32 precision's form. xs [3B][ldx]: the fp32 rows of the blocks in f32mask (route 0
+ * only; bit c: block c) and, once the inexact flag has risen, of those in f32dyn_mask; required only
+ * when a mask names a block. xbits [B][ldbits]: the lock block as bits (optional on route 0). xbf, xbw
+ * (routes 1-3; xbw may be NULL with no_xbw): the BitMats of mvae_debug_pairs_bits, zero-filled by the
+ * caller. dyn: the 4 flag ints; the launch gets dyn + slot as its flags (the inexact word dyn[slot],
+ * the not-binary word dyn[2 + slot], both zero on entry) and zeroes the other slot (dyn[1 - slot],
+ * dyn[3 - slot]). x_elems, xs_elems, planes_elems, xbits_elems: the extents of those buffers.
+ * MVAE_EINVAL with a message, before any HIP call: args or a required buffer NULL, route / np / slot /
+ * a mask out of range, np 0 or f32mask != 0 on routes 1-3, a size < 1, ldx < D, ldbits < D / 8 where
+ * bits are written, an extent smaller than B rows of 3D (x), 3B rows of ldx (xs; times np planes at
+ * plane_stride: planes) or B rows of ldbits, xs or planes not 16-byte aligned, or a shape or alignment
+ * the bits route does not serve (B % 64, D % 8, ldx % 8, x 16-byte, tables 8-byte, coef 16-byte). */
+typedef struct mvae_input_args {
+  int route, B, H, W;
+  int ldx, np, f32mask, f32dyn_mask;
+  int ldbits, no_xbw, slot;
+  float divisor;
+  long long plane_stride;           /* elements between two planes */
+  long long x_elems, xs_elems, planes_elems, xbits_elems;
+  const float* x;
+  const unsigned char* locks;
+  const unsigned char* keys;
+  const int* idx;
+  const int* key_idx;
+  const float* coef;
+  float* xs;
+  unsigned short* planes;
+  unsigned char* xbits;
+  unsigned* xbf;
+  unsigned* xbw;
+  int* dyn;
+} mvae_input_args;
+int mvae_debug_input_planes(const mvae_input_args* args, void* stream);
 
 #ifdef __cplusplus
 }

@@ -128,7 +128,17 @@ class mvae_gemm_args(C.Structure):
                                         "x3", "tm", "split", "group", "epi", "act", "bits", "bits_shared", "a_off",
                                         "b_off")] +
                 [(n, C.c_longlong) for n in ("sA", "sB", "sC", "a_elems", "b_elems", "c_elems")] +
-                [(n, C.c_void_p) for n in ("A", "B", "C")])
+                [(n, C.c_void_p) for n in ("A", "B", "C")] + [("a_dyn", C.c_int)])
+
+
+class mvae_input_args(C.Structure):
+    """Arguments of ``mvae_debug_input_planes`` (``include/mvae.h``): one route of batch input on caller
+    buffers; a zeroed field is a NULL / 0 argument."""
+    _fields_ = ([(n, C.c_int) for n in ("route", "B", "H", "W", "ldx", "np", "f32mask", "f32dyn_mask", "ldbits",
+                                        "no_xbw", "slot")] + [("divisor", C.c_float)] +
+                [(n, C.c_longlong) for n in ("plane_stride", "x_elems", "xs_elems", "planes_elems", "xbits_elems")] +
+                [(n, C.c_void_p) for n in ("x", "locks", "keys", "idx", "key_idx", "coef", "xs", "planes", "xbits",
+                                           "xbf", "xbw", "dyn")])
 
 
 KERNEL_NAMES = {1: "f32", 2: "valu", 3: "plane", 4: "ring", 5: "x3", 6: "e8"}
@@ -242,6 +252,7 @@ _SIGS = {
     "mvae_debug_epi": ([C.POINTER(mvae_epi_args), C.c_void_p], C.c_int),
     "mvae_debug_plan": ([C.POINTER(mvae_plan_args), C.POINTER(mvae_plan_out)], C.c_int),
     "mvae_debug_gemm_ex": ([C.POINTER(mvae_gemm_args), C.POINTER(mvae_plan_out), C.c_void_p], C.c_int),
+    "mvae_debug_input_planes": ([C.POINTER(mvae_input_args), C.c_void_p], C.c_int),
 }
 
 EXPORTED = tuple(_SIGS)

@@ -602,6 +602,88 @@ extern "C" int mvae_debug_xpairs_bits(const unsigned char* locks, const unsigned
                     xbw, xbits, ldbits, dyn, plane, ldx, stream);
 }
 
+// The plane side of batch input on caller buffers (tests only; synchronous; allocates nothing): fills
+// a Planes / BitsDst with every field the step sets -- the fp32 rows and their two masks, one or three
+// planes, the flag slot in use -- and launches one route: the plane path's de-interleave (its form
+// chosen by the caller's x, D and ldx) or a bits launcher, whose grey pass writes the planes.
+// Everything the kernels' addressing relies on is checked here, before any HIP call; include/mvae.h
+// lists the fields.
+extern "C" int mvae_debug_input_planes(const mvae_input_args* args, void* stream) {
+  const char* who = "mvae_debug_input_planes: ";
+  auto bad = [&](const std::string& m) { return fail(nullptr, MVAE_EINVAL, who + m); };
+  if (!args) return bad("args is NULL");
+  const mvae_input_args& a = *args;
+  if (a.route < 0 || a.route > 3) return bad("route must be in [0, 3]");
+  if (a.np != 0 && a.np != 1 && a.np != 3) return bad("np must be 0, 1 or 3");
+  if (a.slot != 0 && a.slot != 1) return bad("slot must be 0 or 1");
+  if ((a.f32mask & ~7) || (a.f32dyn_mask & ~7)) return bad("f32mask and f32dyn_mask must be in [0, 7]");
+  if (a.B < 1 || a.H < 1 || a.W < 1) return bad("B, H and W must be at least 1");
+  if (a.B > 65535 || (long long)a.H * a.W > (1 << 24)) return bad("B or H W too large");  // (B: a grid dimension)
+  const bool bits = a.route != 0;
+  if (bits && a.np == 0) return bad("np 0 is the plane path's (route 0)");
+  if (bits && a.f32mask) return bad("f32mask is the plane path's (route 0)");
+  const int B = a.B, D = a.H * a.W;
+  if (a.ldx < D) return bad("ldx is smaller than a row");
+  if (!a.dyn) return bad("dyn is NULL");
+  const long long rows = 3LL * B * a.ldx;
+  if (a.route <= 1) {
+    if (!a.x) return bad("x is NULL");
+    if (a.x_elems < 3LL * B * D) return bad("x_elems is smaller than the batch");
+  }
+  if (a.route == 2 && (!a.locks || !a.keys || !a.idx || !a.coef)) return bad("locks, keys, idx or coef is NULL");
+  if (a.route == 3 && (!a.locks || !a.idx)) return bad("locks (the table) or idx is NULL");
+  if (a.route >= 2 && !(a.divisor > 0.f)) return bad("divisor must be positive");
+  if (a.np) {
+    if (!a.planes) return bad("planes is NULL");
+    if (a.np == 3 && a.plane_stride < rows) return bad("plane_stride is smaller than a plane");
+    if (a.planes_elems < (a.np - 1) * a.plane_stride + rows) return bad("planes_elems is smaller than the planes");
+    if (misaligned(a.planes)) return bad("planes is not 16-byte aligned");
+  }
+  if (a.f32mask | a.f32dyn_mask) {
+    if (!a.xs) return bad("xs is NULL");
+    if (a.xs_elems < rows) return bad("xs_elems is smaller than the stacked rows");
+    if (misaligned(a.xs)) return bad("xs is not 16-byte aligned");
+  }
+  if (bits && !a.xbits) return bad("xbits is NULL");
+  if (a.xbits) {
+    if (a.ldbits < D / 8) return bad("ldbits is smaller than a row");
+    if (a.xbits_elems < (long long)B * a.ldbits) return bad("xbits_elems is smaller than the rows");
+  }
+  if (bits && (!a.xbf || (!a.no_xbw && !a.xbw))) return bad("xbf or xbw is NULL");
+  if (bits) {  // the launchers' own conditions
+    bool serves = (D % 8) == 0 && (B % 64) == 0 && (a.ldx % 8) == 0;
+    if (a.route == 1) serves = serves && !misaligned(a.x);
+    if (a.route == 2) serves = serves && pairs_bits_fits(a.locks, a.keys, a.coef, B, D);
+    if (a.route == 3) serves = serves && images_bits_fits(a.locks, B, D);
+    if (!serves) return bad("shape or alignment the route does not serve");
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const Planes xp{a.np ? a.planes : nullptr, a.plane_stride, a.np};
+  int* flag = a.dyn + a.slot;
+  int* next = a.dyn + 1 - a.slot;
+  hipError_t e;
+  if (!bits) {
+    e = launch_deinterleave(a.x, a.xs, xp, flag, next, B, D, a.ldx, a.f32mask, a.f32dyn_mask, st, a.xbits, a.ldbits);
+  } else {
+    BitsDst dst;
+    dst.xbf = a.xbf; dst.kts_f = bitmat_kts(D + 1); dst.xbw = a.xbw; dst.kts_w = bitmat_kts(3 * B);
+    dst.xbits = a.xbits; dst.ldbits = a.ldbits; dst.xs = a.xs; dst.xp = xp; dst.ldx = a.ldx;
+    dst.f32dyn_mask = a.f32dyn_mask;
+    const bool now = a.no_xbw != 0;
+    if (a.route == 1)
+      e = launch_deint_bits(XBatch{a.x, B, D}, dst, flag, next, now, st);
+    else if (a.route == 2)
+      e = launch_pairs_bits(PairsBatch{a.locks, a.keys, a.H, a.W, a.idx, a.key_idx, a.coef, a.divisor, B}, dst, flag,
+                            next, now, st);
+    else
+      e = launch_images_bits(ImagesBatch{a.locks, a.H, a.W, a.idx, 3 * B, a.divisor, B}, dst, flag, next, now, st);
+  }
+  if (e == hipErrorInvalidValue) return bad("shape or alignment the route does not serve");
+  DIAG(e);
+  DIAG(hipStreamSynchronize(st));
+  return MVAE_OK;
+}
+
 // The fused hidden-layer chain on caller buffers (tests only; synchronous; allocates nothing): fills a
 // ChainArgs as mvae_plan.cpp's chain_of does and launches the step's kernel. Everything the kernel's
 // addressing relies on is checked here, before any HIP call: it reads 16-B chunks of x up to
@@ -865,8 +947,8 @@ extern "C" int mvae_debug_plan(const mvae_plan_args* args, mvae_plan_out* out) {
 
 // One batched GEMM on caller buffers (tests only; synchronous): the GemmDesc mvae_debug_gemm builds,
 // with what that entry fixes at one value -- the batch and its strides, a forced split, the tile
-// order, the plane images' alignment, the BitMat's two batch forms. Everything the kernels'
-// addressing relies on is checked here, before any HIP call; include/mvae.h lists the fields.
+// order, the plane images' alignment, the BitMat's two batch forms, A's run-time flag. Everything the
+// kernels' addressing relies on is checked here, before any HIP call; include/mvae.h lists the fields.
 extern "C" int mvae_debug_gemm_ex(const mvae_gemm_args* args, mvae_plan_out* plan, void* stream) {
   const char* who = "mvae_debug_gemm_ex: ";
   auto bad = [&](const std::string& m) { return fail(nullptr, MVAE_EINVAL, who + m); };
@@ -903,6 +985,8 @@ extern "C" int mvae_debug_gemm_ex(const mvae_gemm_args* args, mvae_plan_out* pla
   if (a.bits_shared != 0 && a.bits_shared != 1) return bad("bits_shared must be 0 or 1");
   if (a.bits_shared && (!a.bits || !a.at || a.sA % (64LL * a.lda)))
     return bad("bits_shared needs bits, at = 1 and sA a multiple of 64 lda");
+  if (a.a_dyn < 0 || a.a_dyn > 2) return bad("a_dyn must be 0, 1 or 2");
+  if (a.a_dyn && (a.prec != GEMM_F32X || fp32)) return bad("a_dyn needs prec 2");
   hipStream_t st = (hipStream_t)stream;
   Arena ar(st);
   GemmDesc d = gd(a.M, a.N, a.K, a.A, a.lda, a.at != 0, a.B, a.ldb, a.bt != 0, a.C, a.ldc, a.epi);
@@ -947,6 +1031,13 @@ extern "C" int mvae_debug_gemm_ex(const mvae_gemm_args* args, mvae_plan_out* pla
     }
     d.anb = pnb;
     d.bits_reg = a.bits == 2;
+  }
+  if (a.a_dyn) {  // A's run-time flag: a word of 0 (only the pairs with A's plane 0 run) or of 1
+    static const int one = 1;
+    auto* pdyn = ar.alloc<int>(4, true);
+    DIAG(ar.err);
+    if (a.a_dyn == 2) DIAG(hipMemcpyAsync(pdyn, &one, sizeof one, hipMemcpyHostToDevice, st));
+    d.dynA = pdyn;
   }
   const size_t ws_n = gemm_workspace_elems(d);
   float* ws = ws_n ? ar.alloc<float>(ws_n) : nullptr;

@@ -176,10 +176,44 @@ BY_NAME = {c["name"]: c for c in CASES}
 assert len(BY_NAME) == len(CASES)
 
 
+def _pair_cases():
+    """The cases of the plane-pair pins (tests/test_gpu_gemm_pairs.py): the f32x families at the table's
+    smallest shapes that reach each kernel, batch 2, both at and both bt, unsplit and a forced split whose
+    last slice is one partial k-tile (kchunk 192, K 400: k 384..399). A 192-row tile needs a k-contiguous
+    A: those families run at = 0 alone."""
+    fams = [("pairs_plane", 130, 70, dict(variant=4), (0, 1)),
+            ("pairs_ring256", 300, 260, dict(variant=11, tm=256), (0, 1)),
+            ("pairs_ring192", 300, 260, dict(variant=11, tm=192), (0,)),
+            ("pairs_x3f1_256", 300, 260, dict(variant=11, x3=1, tm=256), (0, 1)),
+            ("pairs_x3f1_192", 300, 260, dict(variant=11, x3=1, tm=192), (0,)),
+            ("pairs_x3f2", 300, 260, dict(variant=12, x3=2, tm=256), (0, 1)),
+            ("pairs_e8", 300, 260, dict(variant=13), (0, 1)),
+            ("pairs_e8_bits_lds", 300, 260, dict(variant=13, bits=1), (0, 1)),
+            ("pairs_e8_bits_reg", 300, 260, dict(variant=13, bits=2), (0, 1))]
+    out = []
+    for fam, M, N, kw, ats in fams:
+        for at in ats:
+            for bt in (0, 1):
+                out.append(make(f"{fam}_at{at}_bt{bt}_unsplit", M, N, 200, at=at, bt=bt, split=1, prec=PREC_F32X, **kw))
+                out.append(make(f"{fam}_at{at}_bt{bt}_tail_slice", M, N, 400, at=at, bt=bt, split=3, prec=PREC_F32X,
+                                **kw))
+    # unforced: the planner's own choice, which weighs a flag on A (fewer plane pairs expected)
+    out.append(make("pairs_planner_at1", 300, 260, 576, at=1, prec=PREC_F32X))
+    out.append(make("pairs_planner_bits", 300, 260, 576, at=1, prec=PREC_F32X, bits=2))
+    return out
+
+
+PAIR_CASES = _pair_cases()
+PAIR_BY_NAME = {c["name"]: c for c in PAIR_CASES}
+assert len(PAIR_BY_NAME) == len(PAIR_CASES) and not set(PAIR_BY_NAME) & set(BY_NAME)
+
+
 def fill_args(a, c, **ptrs):
-    """The case's fields (and the pointers given) into an mvae_gemm_args."""
+    """The case's fields (and the pointers given) into an mvae_gemm_args; a_dyn (A's run-time flag) is 0
+    where the case does not name it."""
     for k in FIELDS:
         setattr(a, k, c[k])
+    a.a_dyn = c.get("a_dyn", 0)
     for k, v in ptrs.items():
         setattr(a, k, v)
     return a
@@ -195,6 +229,7 @@ def plan_args(a, c, base):
     a.nA = a.nB = planes
     a.c32 = 1
     a.abits = 1 if c["bits"] else 0
+    a.dynA = 1 if c.get("a_dyn", 0) else 0
     a.pA, a.pB = round8(c["a_elems"]), round8(c["b_elems"])
     a.max_ws = 2 ** 64 - 1
     a.Ap, a.Bp = base + 2 * c["a_off"], base + 2 * c["b_off"]

@@ -52,7 +52,10 @@ def test_debug_gemm_ex_rejects_bad_arguments():
            dict(shared=True, bits=0), dict(shared=True, prec=0),
            dict(shared=True, sA=255 * 304), dict(shared=True, sA=256 * 304 + 8),
            # (at = 0: the same buffers as M 512 x K 300 with sA still a multiple of 64 lda)
-           dict(shared=True, at=0, M=512, K=300, sC=512 * base["ldc"] + 16, c_elems=10 ** 9)]
+           dict(shared=True, at=0, M=512, K=300, sC=512 * base["ldc"] + 16, c_elems=10 ** 9),
+           # A's run-time flag: f32x only (the base case is bf16)
+           dict(a_dyn=1), dict(a_dyn=2), dict(a_dyn=1, prec=0), dict(a_dyn=1, prec=2, variant=9),
+           dict(a_dyn=3, prec=2), dict(a_dyn=-1, prec=2)]
     for b in bad:
         rc = lib.mvae_debug_gemm_ex(ctypes.byref(_args(p, **b)), None, None)
         assert rc == -1, (b, rc)   # MVAE_EINVAL
@@ -70,7 +73,52 @@ def test_abi_version_unchanged():
     names = [n.strip(" *") for decl in fields.split(";") if decl.strip()
              for n in re.sub(r"^\s*(const\s+)?(unsigned\s+)?(long long|\w+)", "", decl.strip()).split(",")]
     assert names == [f[0] for f in _lib.mvae_gemm_args._fields_]
-    assert names == list(G.FIELDS) + ["A", "B", "C"]
+    assert names == list(G.FIELDS) + ["A", "B", "C", "a_dyn"]   # (a_dyn: appended; a zero keeps the old behaviour)
+
+
+# ------------------------------------------------------------------ the plane-pair cases (test_gpu_gemm_pairs.py)
+
+@pytest.fixture(scope="module")
+def pair_plans():
+    """name -> (case, its plan without a flag, its plan with one)."""
+    lib = _lib.load()
+    buf = ctypes.create_string_buffer(64)
+    base = (ctypes.addressof(buf) + 15) & ~15
+    out = {}
+    for c in G.PAIR_CASES:
+        ps = []
+        for a_dyn in (0, 1):
+            a, o = G.plan_args(_lib.mvae_plan_args(), dict(c, a_dyn=a_dyn), base), _lib.mvae_plan_out()
+            assert lib.mvae_debug_plan(ctypes.byref(a), ctypes.byref(o)) == 0, (c["name"], lib.mvae_last_error(None))
+            ps.append({f[0]: getattr(o, f[0]) for f in _lib.mvae_plan_out._fields_})
+        out[c["name"]] = (c, ps[0], ps[1])
+    return out
+
+
+def test_pair_cases_reach_every_f32x_family(pair_plans):
+    """Plane; ring at 256 and 192 rows; the plane-stacked kernel in both forms (tile N 128 at 256 and 192
+    rows, 256x256); eight-phase on planes and on both bits forms -- each with both at (k-contiguous A alone
+    on 192 rows), both bt, unsplit and a split whose last slice is one partial k-tile, at batch 2. A flag
+    on A changes none of these forced plans."""
+    want = {"pairs_plane": (PLANE, 128, 128), "pairs_ring256": (RING, 256, 128), "pairs_ring192": (RING, 192, 128),
+            "pairs_x3f1_256": (X3, 256, 128), "pairs_x3f1_192": (X3, 192, 128), "pairs_x3f2": (X3, 256, 256),
+            "pairs_e8": (E8, 256, 256), "pairs_e8_bits_lds": (E8, 256, 256), "pairs_e8_bits_reg": (E8, 256, 256)}
+    seen = {}
+    for name, (c, p, pd) in pair_plans.items():
+        if name.startswith("pairs_planner"):     # unforced: whatever the planner picks, a 256-row kernel
+            assert (c["variant"], c["split"]) == (0, 0) and p["kernel"] in (RING, X3, E8) and pd["kernel"] == p["kernel"]
+            continue
+        fam = max((k for k in want if name.startswith(k + "_at")), key=len)
+        assert (p["kernel"], p["tm"], p["tn"]) == want[fam], (name, p)
+        assert c["prec"] == G.PREC_F32X and c["batch"] == 2 and not p["refused"]
+        assert p["split"] == c["split"] and p == pd, (name, p, pd)
+        assert _partial_last(c, p) == ("tail_slice" in name) and (p["split"] == 1) == ("unsplit" in name), (name, p)
+        assert (c["bits"] == 1) == ("bits_lds" in name) and (c["bits"] == 2) == ("bits_reg" in name)
+        seen.setdefault(fam, set()).add((c["at"], c["bt"], p["split"] > 1))
+    assert set(seen) == set(want)
+    for fam, s in seen.items():
+        ats = (0,) if "192" in fam else (0, 1)
+        assert s == {(at, bt, sp) for at in ats for bt in (0, 1) for sp in (False, True)}, fam
 
 
 # ------------------------------------------------------------------ the cases are what they say

@@ -511,7 +511,19 @@ int mvae_timing_reset(mvae_ctx* ctx);
  * 1 act (act: 0 tanh, 1 elu), 2 C = acc * act'(aux), 4 sigmoid; epi | (prec << 4) |
  * (variant << 8) selects the arithmetic (MVAE_PREC_*) and the kernel (the table of kernel numbers
  * at mvae_debug_plan below; 0 the planner's choice). Workspace is allocated and freed inside
- * (synchronous; tests only). mvae_bench_gemm: variant | (prec << 4) | (epi << 8).    */
+ * (synchronous; tests only).
+ * mvae_bench_gemm times `iters` launches of one shape on operands it makes itself (average ms in
+ * *avg_ms). Its variant:
+ *    bits 0-3    the kernel number (the same table)
+ *    bits 4-7    prec (MVAE_PREC_*)
+ *    bits 8-11   epi, with the operands the step's epilogue reads (0 store, 1 act, 2 dact, 3 BCE,
+ *                4 sigmoid)
+ *    bits 12-19  refused: MVAE_EINVAL with a message, before anything is allocated (they selected
+ *                kernel timing diagnostics that were removed)
+ *    bit 20      A of 0/1 values (in f32x its residual planes then zero)
+ *    bit 21      with bit 20: A also as a BitMat, the eight-phase kernel's bits path
+ * Of the environment it reads MVAE_BENCH_LDPAD, MVAE_BENCH_SPLIT, MVAE_BENCH_TILE_GROUP and
+ * MVAE_BENCH_PLANES_ONLY. */
 int mvae_bench_gemm(int M, int N, int K, int at, int bt, int batch, int variant, int iters,
                     void* stream, float* avg_ms);
 /* Diagnostics: the step's de-interleave of a [B][3D] batch of random 0/1 pixels, iters launches

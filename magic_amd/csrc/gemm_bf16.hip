@@ -42,13 +42,6 @@ struct Geo {
   static constexpr int NLD = 128 * BK / 8 / NT;                         // 16-B loads / thread
 };
 
-// 100 MHz constant-rate stamp, workgroup-comparable (diagnostics builds only)
-__device__ __forceinline__ unsigned long long realtime() {
-  unsigned long long t;
-  asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) :: "memory");
-  return t;
-}
-
 template <bool KC, int BK>
 struct Stage {
   static constexpr int SK = Geo<BK>::SK;
@@ -128,7 +121,6 @@ __global__ __launch_bounds__(NT, 2) void gemm_bf16p_kernel(PParams pp) {
   constexpr int STAGE = Geo<BK>::STAGE;
   constexpr int NB = DB ? 2 : 1;
   const Params& p = pp.g;
-  if (epi_skip<EPI>(p.epi)) return;
   __shared__ __attribute__((aligned(16))) short smem[2 * NB * STAGE];
   // image b of A at smem + b*STAGE, of B at smem + (NB+b)*STAGE
 
@@ -262,8 +254,6 @@ struct WLoad {
       __builtin_amdgcn_global_load_lds(src, (lds_short*)(img + (j * NW + wave) * 512), 16, 0, 0);
     }
   }
-  // LDS instructions per fragment
-  static constexpr int NRD = KC ? 1 : 2;
   // fragment (8 consecutive k) of the 32-row block at rb, k16-step ks. All fragment reads are
   // inline asm and their results are waited for explicitly (wait_lds) before use: the
   // transposing-read builtin makes hipcc wait for every outstanding LDS-DMA (vmcnt(0)), and a
@@ -293,23 +283,15 @@ struct WLoad {
   }
 };
 
-// wait until at most N LDS instructions are outstanding (N is a literal per instantiation)
-template <int N>
-__device__ __forceinline__ void wait_lds() {
-  if constexpr (N == 0) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  else if constexpr (N == 4) asm volatile("s_waitcnt lgkmcnt(4)" ::: "memory");
-  else if constexpr (N == 6) asm volatile("s_waitcnt lgkmcnt(6)" ::: "memory");
-  else if constexpr (N == 8) asm volatile("s_waitcnt lgkmcnt(8)" ::: "memory");
-  else if constexpr (N == 10) asm volatile("s_waitcnt lgkmcnt(10)" ::: "memory");
-  else if constexpr (N == 12) asm volatile("s_waitcnt lgkmcnt(12)" ::: "memory");
-  else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-}
+// wait until no LDS instruction is outstanding
+__device__ __forceinline__ void wait_lds() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 // wait until at most N vector-memory operations are outstanding (N literal per instantiation)
 template <int N>
 __device__ __forceinline__ void wait_vm() {
   if constexpr (N == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
   else if constexpr (N == 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
   else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+  else if constexpr (N == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
   else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
@@ -330,15 +312,9 @@ __device__ __forceinline__ void wait_vm() {
 // Tile 256 x TN (TN = 256 or 128), 8 waves 2 (M) x 4 (N), each 128 x TN/4 = 4 x NI 32x32
 // accumulators. TN = 128 doubles the tile count of a narrow GEMM (N ~ 500: the hidden encoder
 // and decoder layers) so it fills the chip without split-K slabs and their reduction.
-// MVAE_QGAP (build-time A/B): the next k16-step's fragment reads are spread over the first
-// NM - MVAE_QGAP MFMA gaps, so the last one has MVAE_QGAP more MFMAs to land before the step's
-// lgkmcnt(0)
-#ifndef MVAE_QGAP
-#define MVAE_QGAP 0
-#endif
 // MI = 3 (k-contiguous A only): a 192 x TN tile (each wave 96 x TN/4), so a 3B-row GEMM of
 // 24576 rows is 128 x 2 = 256 workgroups -- one per CU -- instead of 96 x 2 = 192 (256 rows).
-template <bool AT, bool BT, int EPI, bool TE, int TN, int MI = 4, bool ST = false>
+template <bool AT, bool BT, int EPI, bool TE, int TN, int MI = 4>
 __global__ __launch_bounds__(WNT, 1) void gemm_bf16q_kernel(PParams pp) {
   constexpr int BK = 64;
   constexpr int NI = TN / 128;
@@ -349,13 +325,6 @@ __global__ __launch_bounds__(WNT, 1) void gemm_bf16q_kernel(PParams pp) {
   constexpr int NM = MI * NI;                  // MFMAs per wave per k16-step
   constexpr int NF = NI + MI;                  // fragments per wave per k16-step (B first)
   const Params& p = pp.g;
-  if (epi_skip<EPI>(p.epi)) return;
-  unsigned long long st0 = 0, st1 = 0, st2 = 0, st_wait = 0, st_vmw = 0;
-  if constexpr (ST) {
-    __builtin_amdgcn_sched_barrier(0);
-    st0 = realtime();
-    __builtin_amdgcn_sched_barrier(0);
-  }
   // A ring slots | B ring slots; the row-major epilogue's two 64-row bands (and the BCE row
   // partials) reuse it after the k-loop
   constexpr int RING = 3 * IMA + 2 * IMB;
@@ -384,10 +353,7 @@ __global__ __launch_bounds__(WNT, 1) void gemm_bf16q_kernel(PParams pp) {
 
   const int np = (pp.dyn && *pp.dyn == 0) ? pp.npairs0 : pp.npairs;
   const int nkt = t.ks < t.ke ? (t.ke - t.ks + BK - 1) / BK : 0;
-  const int total = (pp.diag & 16) ? 0 : np * nkt;  // diag bit 4: the epilogue alone
-  // s_setprio 1 around each k16-step's MFMAs (cdna_hip_programming.md T5): +1-3 % on the step's
-  // GEMMs, +3-7 % on 4096^3 (profiles/r3/gemm_ab_setprio_r3u.txt); diag bit 5 turns it off (A/B)
-  const bool sprio = (pp.diag & 32) == 0;
+  const int total = np * nkt;
   const unsigned lds0 = (unsigned)(uintptr_t)(lds_short*)smem;
   auto pa_of = [&](int pr) { return (pp.pab >> (4 * pr)) & 3; };
   auto pb_of = [&](int pr) { return (pp.pab >> (4 * pr + 2)) & 3; };
@@ -396,11 +362,10 @@ __global__ __launch_bounds__(WNT, 1) void gemm_bf16q_kernel(PParams pp) {
   int akt = 0, apr = 0, ia = 0, asl = 0;
   int bkt = 0, bpr = 0, ib = 0, bsl = 0;
   bool pend_a = false;  // the A copy issued with the last B copy (vmcnt accounting)
-  const bool dma = !(pp.diag & 1);
   constexpr int GA = WLoad<!AT, BK, TM>::NG;  // DMA instructions per A image per thread
   // move the A cursor to ia+1 and copy its image if it differs from ia's
   auto next_a = [&]() -> bool {
-    if (ia + 1 >= total || !dma) return false;
+    if (ia + 1 >= total) return false;
     const int k0 = akt, p0 = apr;
     adv(akt, apr);
     ++ia;
@@ -410,7 +375,7 @@ __global__ __launch_bounds__(WNT, 1) void gemm_bf16q_kernel(PParams pp) {
     return true;
   };
   auto next_b = [&]() -> bool {
-    if (ib + 1 >= total || !dma) return false;
+    if (ib + 1 >= total) return false;
     const int k0 = bkt, p0 = bpr;
     adv(bkt, bpr);
     ++ib;
@@ -454,11 +419,6 @@ __global__ __launch_bounds__(WNT, 1) void gemm_bf16q_kernel(PParams pp) {
     }
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-    if constexpr (ST) {
-      __builtin_amdgcn_sched_barrier(0);
-      st1 = realtime();
-      __builtin_amdgcn_sched_barrier(0);
-    }
     next_b();
     sb_q[0] = 0; sb_q[1] = bsl;
     pend_a = next_a();
@@ -471,9 +431,11 @@ __global__ __launch_bounds__(WNT, 1) void gemm_bf16q_kernel(PParams pp) {
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
       const int cur = ks & 1, nx = cur ^ 1;
-      wait_lds<0>();  // this step's fragments (read during the previous step's MFMAs)
+      wait_lds();  // this step's fragments (read during the previous step's MFMAs)
       __builtin_amdgcn_sched_barrier(0);
-      if (sprio) __builtin_amdgcn_s_setprio(1);
+      // s_setprio 1 around each k16-step's MFMAs (cdna_hip_programming.md T5): +1-3 % on the step's
+      // GEMMs, +3-7 % on 4096^3 (profiles/r3/gemm_ab_setprio_r3u.txt)
+      __builtin_amdgcn_s_setprio(1);
       if (ks + 1 < KS) {
         // MFMA i, then the fragments of step ks+1 assigned to its gap
 #pragma unroll
@@ -482,7 +444,7 @@ __global__ __launch_bounds__(WNT, 1) void gemm_bf16q_kernel(PParams pp) {
           __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
           for (int f = 0; f < NF; ++f)
-            if (f * (NM - MVAE_QGAP) / NF == i) rd_f(sa, sb, ks + 1, f, nx);
+            if (f * NM / NF == i) rd_f(sa, sb, ks + 1, f, nx);
           __builtin_amdgcn_sched_barrier(0);
         }
       } else {
@@ -491,8 +453,6 @@ __global__ __launch_bounds__(WNT, 1) void gemm_bf16q_kernel(PParams pp) {
         __builtin_amdgcn_sched_barrier(0);
         const bool more = it + 1 < total;
         if (more) {
-          unsigned long long tw0 = 0;
-          if constexpr (ST) tw0 = realtime();
           // images of it+1 landed (only the A copy issued after its B copy may be in flight),
           // every wave's reads of it's images are done: its freed slots can be refilled
           if (pend_a) {
@@ -500,14 +460,8 @@ __global__ __launch_bounds__(WNT, 1) void gemm_bf16q_kernel(PParams pp) {
           } else {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
           }
-          if constexpr (ST) {  // stamped builds: time in the vmcnt wait, then in the barrier
-            const unsigned long long tw1 = realtime();
-            st_vmw += tw1 - tw0;
-            tw0 = tw1;
-          }
           __builtin_amdgcn_s_barrier();
           asm volatile("" ::: "memory");
-          if constexpr (ST) st_wait += realtime() - tw0;
         }
         __builtin_amdgcn_sched_barrier(0);
         // fragments of it+1's first step (its images: the slot queues' second entries), then
@@ -531,47 +485,23 @@ __global__ __launch_bounds__(WNT, 1) void gemm_bf16q_kernel(PParams pp) {
           __builtin_amdgcn_sched_barrier(0);
         }
       }
-      if (sprio) __builtin_amdgcn_s_setprio(0);
+      __builtin_amdgcn_s_setprio(0);
       __builtin_amdgcn_sched_barrier(0);
     }
     // KS is even: the next iteration's step 0 reads land in fa/fb[0]
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  if constexpr (ST) {
-    __builtin_amdgcn_sched_barrier(0);
-    st2 = realtime();
-    __builtin_amdgcn_sched_barrier(0);
-  }
-  unsigned long long st_iss = 0;
   // BCE row partials in the LDS past the two 64-row bands (2 x 64 x TN floats), 64 MI x TN / 8
   // floats (EPIL above)
-  if constexpr (TE) epilogue_rm<EPI, MI, NI, 4, WNT>(p, t, acc, reinterpret_cast<float*>(smem), wm, wn, pp.diag,
-                                                     ST ? &st_iss : nullptr,
+  if constexpr (TE) epilogue_rm<EPI, MI, NI, 4, WNT>(p, t, acc, reinterpret_cast<float*>(smem), wm, wn,
                                                      reinterpret_cast<float*>(smem) + 2 * 64 * TN);
   else epilogue_g<EPI, MI, NI, TM, 4>(p, t, acc, reinterpret_cast<float*>(smem), wm, wn);
-  if constexpr (ST) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    const unsigned long long st3 = realtime();
-    if (threadIdx.x == 0) {
-      unsigned long long* o = pp.stamps + 8 * (size_t)blockIdx.x;
-      o[0] = st0; o[1] = st1; o[2] = st2; o[3] = st3; o[4] = st_iss; o[5] = st_wait; o[6] = st_vmw;
-    }
-  }
 }
 
 template <bool AT, bool BT, int EPI, bool TE, int TN, int MI = 4>
 hipError_t launch_q(const PParams& p, hipStream_t st) {
   const int nwg = p.g.ntm * p.g.ntn * p.g.batch * p.g.split;
-  // stamped diagnostics builds (bench only): the hidden forward (ACT), the BCE head (BCEB, bf16 binary target as in the step) and
-  // the hidden dgrad (DACTB: bf16 aux, B = W^T)
-  if constexpr (TE && !AT && ((EPI == EPI_ACT && !BT) || (EPI == EPI_BCEB && !BT) || (EPI == EPI_DACTB && BT))) {
-    if (p.stamps) {
-      hipLaunchKernelGGL((gemm_bf16q_kernel<AT, BT, EPI, TE, TN, MI, true>), dim3(nwg), dim3(WNT), 0, st, p);
-      return hipGetLastError();
-    }
-  }
   hipLaunchKernelGGL((gemm_bf16q_kernel<AT, BT, EPI, TE, TN, MI>), dim3(nwg), dim3(WNT), 0, st, p);
   return hipGetLastError();
 }
@@ -628,7 +558,6 @@ __device__ __forceinline__ void x3_kloop(const PParams& pp, const Tile& t, const
   la.init(p.lda, t.m0, p.M, wave, lane);
   lb.init(p.ldb, t.n0, p.N, wave, lane);
   const int nkt = t.ks < t.ke ? (t.ke - t.ks + BK - 1) / BK : 0;
-  const bool sprio = (pp.diag & 32) == 0;
   const unsigned lds0 = (unsigned)(uintptr_t)(lds_short*)smem;
   auto issue = [&](int kt, int st) {
     const int k0 = t.ks + kt * BK;
@@ -672,9 +601,9 @@ __device__ __forceinline__ void x3_kloop(const PParams& pp, const Tile& t, const
   for (int kt = 0; kt < nkt; ++kt) {
     const int st = kt & 1;
     // k16-step 0: its fragments landed; step 1's read into buffer 1 between the MFMAs
-    wait_lds<0>();
+    wait_lds();
     __builtin_amdgcn_sched_barrier(0);
-    if (sprio) __builtin_amdgcn_s_setprio(1);
+    __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int i = 0; i < NM; ++i) {
       mfma(i, 0);
@@ -684,14 +613,14 @@ __device__ __forceinline__ void x3_kloop(const PParams& pp, const Tile& t, const
         if (f * NM / NF == i) rd_f(st, 1, f, 1);
       __builtin_amdgcn_sched_barrier(0);
     }
-    if (sprio) __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_s_setprio(0);
     // k16-step 1: once its fragments are in registers this wave reads stage st no more; after
     // half its MFMAs wait for stage st ^ 1 (k-tile kt + 1, the only copy in flight), one barrier
     // (every wave done with stage st), then the copy of k-tile kt + 2 into stage st and the next
     // k-tile's step-0 fragments behind the remaining MFMAs
-    wait_lds<0>();
+    wait_lds();
     __builtin_amdgcn_sched_barrier(0);
-    if (sprio) __builtin_amdgcn_s_setprio(1);
+    __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int i = 0; i < H; ++i) mfma(i, 1);
     __builtin_amdgcn_sched_barrier(0);
@@ -714,7 +643,7 @@ __device__ __forceinline__ void x3_kloop(const PParams& pp, const Tile& t, const
       }
       __builtin_amdgcn_sched_barrier(0);
     }
-    if (sprio) __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_s_setprio(0);
     __builtin_amdgcn_sched_barrier(0);
   }
 }
@@ -737,7 +666,6 @@ __device__ __forceinline__ void x3w_kloop(const PParams& pp, const Tile& t, cons
   la.init(p.lda, t.m0, p.M, wave, lane);
   lb.init(p.ldb, t.n0, p.N, wave, lane);
   const int nkt = t.ks < t.ke ? (t.ke - t.ks + BK - 1) / BK : 0;
-  const bool sprio = (pp.diag & 32) == 0;
   const unsigned lds0 = (unsigned)(uintptr_t)(lds_short*)smem;
   const bool live = t.n0 + wn * (TN / 4) < p.N;
   auto issue = [&](int kt, int st) {
@@ -755,9 +683,7 @@ __device__ __forceinline__ void x3w_kloop(const PParams& pp, const Tile& t, cons
     // stage kt landed (only k-tile kt + 1's copies may still be in flight), every wave done with
     // k-tile kt - 1's stage: the copy of kt + 2 goes into it
     if (kt + 1 < nkt) {
-      if constexpr (NG == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-      else if constexpr (NG == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      wait_vm<NG>();
     } else {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
@@ -780,9 +706,9 @@ __device__ __forceinline__ void x3w_kloop(const PParams& pp, const Tile& t, cons
         const int o = st * STG + a * IMA;
         fa[a][mi] = la.frag(smem + o, lds0 + 2u * (unsigned)o, wm * (MI * 32) + mi * 32, 0, lane);
       }
-    wait_lds<0>();
+    wait_lds();
     __builtin_amdgcn_sched_barrier(0);
-    if (sprio) __builtin_amdgcn_s_setprio(1);
+    __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int pr = 0; pr < NP; ++pr)
 #pragma unroll
@@ -791,7 +717,7 @@ __device__ __forceinline__ void x3w_kloop(const PParams& pp, const Tile& t, cons
         for (int ni = 0; ni < NI; ++ni)
           acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[x3_pa(NA, NB, pr)][mi], fb[x3_pb(NA, NB, pr)][ni],
                                                                 acc[mi][ni], 0, 0, 0);
-    if (sprio) __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_s_setprio(0);
     __builtin_amdgcn_sched_barrier(0);
   }
 }
@@ -800,7 +726,6 @@ template <bool AT, bool BT, int EPI, bool TE>
 __global__ __launch_bounds__(WNT, 1) void gemm_bf16xw_kernel(PParams pp) {
   constexpr int TM = 256, TN = 256;
   const Params& p = pp.g;
-  if (epi_skip<EPI>(p.epi)) return;
   constexpr int RING = 3 * (3 * TM * 16 + 3 * TN * 16);
   constexpr int EPIL = TE ? 2 * (2 * 64 * TN + 64 * 4 * (TN / 8)) : 0;
   __shared__ __attribute__((aligned(16))) short smem[RING > EPIL ? RING : EPIL];
@@ -817,13 +742,11 @@ __global__ __launch_bounds__(WNT, 1) void gemm_bf16xw_kernel(PParams pp) {
     for (int j = 0; j < 2; ++j)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-  if (!(pp.diag & 16)) {
-    if (pp.dyn && *pp.dyn == 0) x3w_kloop<1, 3, AT, BT>(pp, t, A, Bm, smem, acc, wave, lane, wm, wn);
-    else x3w_kloop<3, 3, AT, BT>(pp, t, A, Bm, smem, acc, wave, lane, wm, wn);
-  }
+  if (pp.dyn && *pp.dyn == 0) x3w_kloop<1, 3, AT, BT>(pp, t, A, Bm, smem, acc, wave, lane, wm, wn);
+  else x3w_kloop<3, 3, AT, BT>(pp, t, A, Bm, smem, acc, wave, lane, wm, wn);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  if constexpr (TE) epilogue_rm<EPI, 4, 2, 4, WNT>(p, t, acc, reinterpret_cast<float*>(smem), wm, wn, pp.diag, nullptr,
+  if constexpr (TE) epilogue_rm<EPI, 4, 2, 4, WNT>(p, t, acc, reinterpret_cast<float*>(smem), wm, wn,
                                                    reinterpret_cast<float*>(smem) + 2 * 64 * TN);
   else epilogue_g<EPI, 4, 2, TM, 4>(p, t, acc, reinterpret_cast<float*>(smem), wm, wn);
 }
@@ -833,7 +756,6 @@ __global__ __launch_bounds__(WNT, 1) void gemm_bf16x_kernel(PParams pp) {
   constexpr int TM = 64 * MI, TN = 128;
   static_assert(MI == 4 || (MI == 3 && !AT), "192-row tiles need a k-contiguous A operand");
   const Params& p = pp.g;
-  if (epi_skip<EPI>(p.epi)) return;
   constexpr int RING = 2 * (3 * TM * 32 + 3 * TN * 32);
   constexpr int EPIL = TE ? 2 * (2 * 64 * TN + 64 * MI * (TN / 8)) : 0;
   __shared__ __attribute__((aligned(16))) short smem[RING > EPIL ? RING : EPIL];
@@ -848,13 +770,11 @@ __global__ __launch_bounds__(WNT, 1) void gemm_bf16x_kernel(PParams pp) {
   for (int i = 0; i < MI; ++i)
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[i][0][r] = 0.f;
-  if (!(pp.diag & 16)) {  // diag bit 4: the epilogue alone
-    if (pp.dyn && *pp.dyn == 0) x3_kloop<1, 3, MI, AT, BT>(pp, t, A, Bm, smem, acc, wave, lane, wm, wn);
-    else x3_kloop<3, 3, MI, AT, BT>(pp, t, A, Bm, smem, acc, wave, lane, wm, wn);
-  }
+  if (pp.dyn && *pp.dyn == 0) x3_kloop<1, 3, MI, AT, BT>(pp, t, A, Bm, smem, acc, wave, lane, wm, wn);
+  else x3_kloop<3, 3, MI, AT, BT>(pp, t, A, Bm, smem, acc, wave, lane, wm, wn);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  if constexpr (TE) epilogue_rm<EPI, MI, 1, 4, WNT>(p, t, acc, reinterpret_cast<float*>(smem), wm, wn, pp.diag, nullptr,
+  if constexpr (TE) epilogue_rm<EPI, MI, 1, 4, WNT>(p, t, acc, reinterpret_cast<float*>(smem), wm, wn,
                                                     reinterpret_cast<float*>(smem) + 2 * 64 * TN);
   else epilogue_g<EPI, MI, 1, TM, 4>(p, t, acc, reinterpret_cast<float*>(smem), wm, wn);
 }
@@ -932,11 +852,8 @@ hipError_t gemm_bf16_launch(const gemm::Params& g, const GemmDesc& d, const Gemm
   p.A = d.Ap; p.pA = d.pA;
   p.B = d.Bp; p.pB = d.pB;
   p.dyn = d.dynA;
-  p.diag = d.diag;
-  p.stamps = d.stamps;
   p.abits = d.Abits; p.abits_kts = d.abits_kts; p.abits_sb = d.abits_sb; p.anb = d.anb;
   p.bits_reg = d.bits_reg;
-  p.x3 = d.x3;
   // plane pairs (i, j), i + j < max(nA, nB); the pairs with i = 0 first, j snaking (ascending for
   // even i, descending for odd i): (0,0) (0,1) (0,2) (1,1) (1,0) (2,0), so consecutive pairs share
   // the B plane at both A-plane changes and the ring kernel copies 3 A + 5 B images per k-tile

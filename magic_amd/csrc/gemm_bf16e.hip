@@ -193,14 +193,12 @@ __device__ __forceinline__ void bits_expand(u32x2 w, bf16x8 (&fa)[8]) {
   }
 }
 
-// main-loop state of one workgroup (registers once inlined). ST: stamped diagnostics build --
-// per wave the k-loop's shader-clock cycles and, with diag 16, each of a k-tile's 8
-// barrier-delimited slots summed over the k-loop (mvae_bench_gemm with MVAE_STAMPS=2; never in
-// the step). BITS: A from a BitMat, its fragments expanded in registers per wave (the plane
-// path's A images, reads and DMA unused) -- 1: each k-tile's block copied into LDS by one
+// main-loop state of one workgroup (registers once inlined). BITS: A from a BitMat, its
+// fragments expanded in registers per wave (the plane path's A images, reads and DMA unused) --
+// 1: each k-tile's block copied into LDS by one
 // 256-B LDS-DMA per wave, each wave reading its two quarters from there; 2: each wave loads its
 // two quarters' words straight into registers (two 8-B `sc1` loads per lane)
-template <bool AT, bool BT, bool ST = false, int BITS = 0>
+template <bool AT, bool BT, int BITS = 0>
 struct E8 {
   static constexpr bool KA = !AT, KB = BT;  // operand images k-contiguous?
   HLoad<KA> la;
@@ -216,8 +214,6 @@ struct E8 {
   const unsigned short* Bm;
   short* smem;
   int wave;
-  unsigned long long st_last, st_acc[ST ? 8 : 1];
-  bool st_slots;  // stamped builds, diag 16: per-slot stamps (each waits lgkmcnt(0): intrusive)
   // BITS: this tile's strip (its first k-tile's block at Ab + 512 * (ks / 64)); LDS byte address
   // of this wave's quarter-0 words in bits buffer 0 (quarter 1: + 1024, buffer 1: + 2048); the
   // current k-tile's words of quarters 0 (A-sub 0) and 1 (A-sub 1)
@@ -248,18 +244,6 @@ struct E8 {
     const unsigned* q = Ab + (size_t)(t.ks / EBK + kt) * BITMAT_BLOCK_WORDS + 2 * wq + 256 * Q;
     if constexpr (Q == 0) asm volatile("global_load_dwordx2 %0, %1, off sc1" : "=v"(wn0) : "v"(q) : "memory");
     else asm volatile("global_load_dwordx2 %0, %1, off sc1" : "=v"(wn1) : "v"(q) : "memory");
-  }
-
-  template <int K>
-  __device__ __forceinline__ void sbar() {
-    bar();
-    if constexpr (ST) {
-      if (!st_slots) return;
-      const unsigned long long t = __builtin_amdgcn_s_memtime();
-      st_acc[K] += t - st_last;
-      st_last = t;
-      __builtin_amdgcn_sched_barrier(0);
-    }
   }
 
   // A half H of buffer Bf at byte (2 H + Bf) EHB; B half H at (4 + 2 H + Bf) EHB (aB includes 4 EHB)
@@ -334,13 +318,10 @@ struct E8 {
   __device__ __forceinline__ void tile(const PParams& pp, const Tile& t, int it, int total, int kt1, int pr1,
                                        int kt2, int pr2, bool ka1, bool ka2, bool kb2, bool ex = true) {
     constexpr int Bn = Bf ^ 1;
-    // stamped builds' A/B switches (results meaningless): diag 1 = no DMA after the prologue,
-    // 64 = no fragment reads
-    const bool dma = !ST || !(pp.diag & 1), rdf = !ST || !(pp.diag & 64);
-    const bool h1 = it + 1 < total && dma, h2 = it + 2 < total && dma;
+    const bool h1 = it + 1 < total, h2 = it + 2 < total;
     const bool ia2 = h2 && !ka2, ib2 = h2 && !kb2;
     // p1 (0,0)
-    if (rdf) rd_b<0, Bf>(fb0);
+    rd_b<0, Bf>(fb0);
     __builtin_amdgcn_sched_barrier(0);
     if constexpr (BITS == 2) {
       // quarter 0 of this k-tile (landed by the last p4's wait) expanded, then it+1's quarter 0
@@ -365,22 +346,22 @@ struct E8 {
         bits_expand(wb0, fa0);
       }
     } else {
-      if (rdf) rd_a<0, Bf>(fa0);
+      rd_a<0, Bf>(fa0);
       if (h1 && !ka1) issue_a<1, Bn>(pp, t, kt1, pr1);
       // the B-sub 0 reads (issued first) retired: B0 is restaged in p2
       // (the A-sub 0 reads: 8 ds_read_b128, or 16 transposing reads -- the count saturates at 15)
       if constexpr (KA) asm volatile("s_waitcnt lgkmcnt(8)" ::: "memory");
       else asm volatile("s_waitcnt lgkmcnt(15)" ::: "memory");
     }
-    sbar<0>();
+    bar();
     mfma_q<0, 0>(fa0, fb0);
-    sbar<1>();
+    bar();
     // p2 (0,1)
-    if (rdf) rd_b<1, Bf>(fb1);
+    rd_b<1, Bf>(fb1);
     if (ib2) issue_b<0, Bf>(pp, t, kt2, pr2);
-    sbar<2>();
+    bar();
     mfma_q<0, 1>(fa0, fb1);
-    sbar<3>();
+    bar();
     // p3 (1,1)
     if constexpr (BITS == 2) {
       // quarter 1 (loaded in the last p3: what is younger may stay in flight except this tile's
@@ -396,12 +377,12 @@ struct E8 {
     } else if constexpr (BITS == 1) {
       if (ex) bits_expand(wb1, fa1);
     } else {
-      if (rdf) rd_a<1, Bf>(fa1);
+      rd_a<1, Bf>(fa1);
       if (ia2) issue_a<0, Bf>(pp, t, kt2, pr2);
     }
-    sbar<4>();
+    bar();
     mfma_q<1, 1>(fa1, fb1);
-    sbar<5>();
+    bar();
     // p4 (1,0): k-tile it+1 landed -- what stays in flight is the halves of it+2 issued in this
     // tile (2 DMA instructions each; the bits path's block of it+1 went out in p1, before them)
     if (ib2) issue_b<1, Bf>(pp, t, kt2, pr2);
@@ -414,31 +395,28 @@ struct E8 {
       else if (ia2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
       else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
-    sbar<6>();
+    bar();
     mfma_q<1, 0>(fa1, fb0);
-    sbar<7>();
+    bar();
   }
 };
 
 // One workgroup's tile: the k-loop and the epilogue. BITS: A from the BitMat pp.abits (its AT
 // is then immaterial: the bits path has one A layout)
-template <bool AT, bool BT, int EPI, bool TE, bool ST, int BITS>
+template <bool AT, bool BT, int EPI, bool TE, int BITS>
 __device__ __forceinline__ void e8_tile(const PParams& pp, short* smem) {
   const Params& p = pp.g;
-  unsigned long long st_k0 = 0, st_k2 = 0;  // stamped builds: kernel start, k-loop end (realtime)
-  if constexpr (ST) st_k0 = __builtin_amdgcn_s_memrealtime();
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 2, wn = wave & 3;
   const Tile t = tile_of_t<256, 256>(p, true);
 
-  using S = E8<AT, BT, ST, BITS>;
+  using S = E8<AT, BT, BITS>;
   S s;
   s.A = pp.A + t.bi * p.sA;
   s.Bm = pp.B + t.bi * p.sB;
   s.smem = smem;
   s.wave = __builtin_amdgcn_readfirstlane(wave);
-  if constexpr (ST) s.st_slots = (pp.diag & 16) != 0;
   if constexpr (BITS) {
     s.Ab = pp.abits + (size_t)t.bi * pp.abits_sb + (size_t)(t.m0 / 256) * pp.abits_kts * BITMAT_BLOCK_WORDS;
   } else {
@@ -476,8 +454,7 @@ __device__ __forceinline__ void e8_tile(const PParams& pp, short* smem) {
   const int nkt = t.ks < t.ke ? (t.ke - t.ks + EBK - 1) / EBK : 0;
   const int total = np * nkt;
   // waves 4-7 (the second wave of every SIMD), as a scalar condition: s_barrier ignores EXEC
-  // (stamped builds, diag 128: no stagger -- both halves in the same phase)
-  const bool lag = __builtin_amdgcn_readfirstlane(wave) >= 4 && !(ST && (pp.diag & 128));
+  const bool lag = __builtin_amdgcn_readfirstlane(wave) >= 4;
 
   if (total > 0) {
     // The (k-tile, pair) walk. Default: pairs innermost. reuse (f32x plane pairs): k-tiles in
@@ -544,13 +521,6 @@ __device__ __forceinline__ void e8_tile(const PParams& pp, short* smem) {
     }
     bar();
     if (lag) bar();
-    unsigned long long st_t0 = 0, st_r0 = 0;
-    if constexpr (ST) {
-#pragma unroll
-      for (int k = 0; k < 8; ++k) s.st_acc[k] = 0;
-      st_r0 = __builtin_amdgcn_s_memrealtime();
-      st_t0 = s.st_last = __builtin_amdgcn_s_memtime();
-    }
     auto step = [&]() { cm = c0; c0 = c1; c1 = c2; adv(c2); };
     // the bits path: it+1's block is copied only for a new k-tile, and an iteration expands only
     // when its k-tile is not it-1's
@@ -567,17 +537,6 @@ __device__ __forceinline__ void e8_tile(const PParams& pp, short* smem) {
       }
     }
     if (!lag) bar();
-    if constexpr (ST) {
-      const unsigned long long t1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
-      if (lane == 0) {
-        unsigned long long* o = pp.stamps + 16 * ((size_t)blockIdx.x * 8 + wave);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) o[k] = s.st_acc[k];
-        o[8] = t1 - st_t0; o[9] = r1 - st_r0; o[10] = total;
-        o[11] = st_r0 - st_k0;  // prologue (realtime ticks, 100 MHz)
-      }
-      st_k2 = r1;
-    }
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
@@ -607,23 +566,17 @@ __device__ __forceinline__ void e8_tile(const PParams& pp, short* smem) {
 #pragma unroll
             for (int k = 0; k < 2; ++k) s.acc[b][i][j][k] = s.acc[b + 1][i][j][k];
     };
-    epilogue_rm_w<EPI, 4, 256, ENT, decltype(wb)&, 1>(p, t, wb, lds_f, 0, nullptr, lds_f + 2 * 64 * 256, TE);
-  }
-  if constexpr (ST) {  // epilogue: from the k-loop's end until every store of the workgroup issued
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (lane == 0 && st_k2) pp.stamps[16 * ((size_t)blockIdx.x * 8 + wave) + 12] = __builtin_amdgcn_s_memrealtime() - st_k2;
+    epilogue_rm_w<EPI, 4, 256, ENT, decltype(wb)&, 1>(p, t, wb, lds_f, lds_f + 2 * 64 * 256, TE);
   }
 }
 
 // the bits path is compiled where the step runs it: the layer-0 forward (ACT, or split-K slabs)
 // and weight gradient (slabs or output), B row-contiguous
-template <bool BT, int EPI, bool ST>
-constexpr bool has_bits = !BT && !ST && (EPI == EPI_STORE || EPI == EPI_ACT);
+template <bool BT, int EPI>
+constexpr bool has_bits = !BT && (EPI == EPI_STORE || EPI == EPI_ACT);
 
-template <bool AT, bool BT, int EPI, bool TE, bool ST = false>
+template <bool AT, bool BT, int EPI, bool TE>
 __global__ __launch_bounds__(ENT, 1) void gemm_bf16e_kernel(PParams pp) {
-  if (epi_skip<EPI>(pp.g.epi)) return;
   // [A0 b0 | A0 b1 | A1 b0 | A1 b1 | B0 b0 | B0 b1 | B1 b0 | B1 b1]; the row-major epilogue's two
   // 64-row bands and the BCE row partials reuse it after the k-loop (one __shared__ array: a
   // second one can make hipcc wait vmcnt(0) before the loop's LDS reads)
@@ -632,25 +585,19 @@ __global__ __launch_bounds__(ENT, 1) void gemm_bf16e_kernel(PParams pp) {
   constexpr int SM = RING > EPIL ? RING : EPIL;
   __shared__ __attribute__((aligned(1024))) short smem[SM];
   // a 0/1 batch (the de-interleave's not-binary word, a uniform branch): A from its bits
-  if constexpr (has_bits<BT, EPI, ST>) {
+  if constexpr (has_bits<BT, EPI>) {
     if (pp.abits && (!pp.anb || *pp.anb == 0)) {
-      if (pp.bits_reg) e8_tile<false, BT, EPI, TE, ST, 2>(pp, smem);
-      else e8_tile<false, BT, EPI, TE, ST, 1>(pp, smem);
+      if (pp.bits_reg) e8_tile<false, BT, EPI, TE, 2>(pp, smem);
+      else e8_tile<false, BT, EPI, TE, 1>(pp, smem);
       return;
     }
   }
-  e8_tile<AT, BT, EPI, TE, ST, 0>(pp, smem);
+  e8_tile<AT, BT, EPI, TE, 0>(pp, smem);
 }
 
 template <bool AT, bool BT, int EPI, bool TE>
 hipError_t launch_e(const PParams& p, hipStream_t st) {
   const int nwg = p.g.ntm * p.g.ntn * p.g.batch * p.g.split;
-  if constexpr (EPI == EPI_STORE) {  // the stamped diagnostics build (mvae_bench_gemm)
-    if (p.stamps) {
-      hipLaunchKernelGGL((gemm_bf16e_kernel<AT, BT, EPI, TE, true>), dim3(nwg), dim3(ENT), 0, st, p);
-      return hipGetLastError();
-    }
-  }
   hipLaunchKernelGGL((gemm_bf16e_kernel<AT, BT, EPI, TE>), dim3(nwg), dim3(ENT), 0, st, p);
   return hipGetLastError();
 }

@@ -36,13 +36,9 @@ struct PParams {
   unsigned char pa[6], pb[6];
   int pab;                          // pa[i] | pb[i] << 2 packed 4 bits per pair (no memory reads)
   const int* dyn;                   // A residual planes nonzero? (nullptr: use all pairs)
-  int diag;                         // timing diagnostics: bit 0 = no operand copies after the
-                                    // prologue (the k-loop multiplies stale LDS images)
   int reuse;                        // eight-phase kernel: (k-tile, pair) iterations in pairs of
                                     // k-tiles, pairs between, and an operand image not copied
                                     // again when its buffer already holds it (gemm_bf16e.hip)
-  unsigned long long* stamps;       // stamped diagnostics builds (ST): 8 slots per workgroup
-                                    // {start, prologue landed, k-loop done, end, stores issued}
   // eight-phase kernel: A as a BitMat (mvae_internal.h) instead of its planes while *anb == 0 --
   // strips of kts blocks per 256 rows, batch stride sb words (GemmDesc::Abits)
   const unsigned* abits = nullptr;
@@ -51,7 +47,6 @@ struct PParams {
   const int* anb = nullptr;
   int npairs_a0 = 1;                // the leading pairs with A plane 0 (the bits path's pairs)
   int bits_reg = 0;                 // eight-phase bits path: A words by loads to registers (E8 BITS 2)
-  int x3 = 0;                       // f32x ring plans at tile N 128: the plane-stacked kernel (GemmDesc::x3)
 };
 
 // tanh as an odd [13/6] rational in x on [-7.905, 7.905] (clamped beyond, where tanh rounds to
@@ -127,13 +122,8 @@ __device__ __forceinline__ float bf16_bits_to_f32(unsigned short b) {
 }
 // BCE epilogues: EPI_BCE reads the fp32 target; EPI_BCEB reads its bf16 plane while *xdyn == 0
 // (every pixel of the batch a bf16 value) and the fp32 target otherwise -- one launch, the
-// choice a uniform branch in the epilogue (bce_x16). An EPI_BCE launch given xdyn returns at once
-// when the plane applies (the two-launch form; gemm_run launches EPI_BCEB alone).
-template <int EPI>
-__device__ __forceinline__ bool epi_skip(const GemmEpi& e) {
-  if constexpr (EPI == EPI_BCE) return e.xdyn != nullptr && *e.xdyn == 0;
-  return false;
-}
+// choice a uniform branch in the epilogue (bce_x16). gemm_run passes xdyn to an EPI_BCEB launch
+// alone and nulls it for every other one, so no kernel has to test it for EPI_BCE.
 // the BCE target read from its bf16 plane?
 template <int EPI>
 __device__ __forceinline__ bool bce_x16(const GemmEpi& e) {
@@ -366,12 +356,10 @@ __device__ __forceinline__ void st8_planes(unsigned short* cp, long long pc, int
   }
 }
 
-// diag (timing diagnostics, results meaningless): bit 1 = no global stores, bit 2 = no LDS
-// transpose, bit 3 = no transcendental math. Waves 2 (M) x NWN (N), NTH threads, each wave
-// acc[MI][NI] 32x32 blocks: tile (64*MI) x TW, TW = NWN*NI*32 (a multiple of 128). Band mi =
+// Waves 2 (M) x NWN (N), NTH threads, each wave acc[MI][NI] 32x32 blocks: tile (64*MI) x TW,
+// TW = NWN*NI*32 (a multiple of 128). Band mi =
 // accumulator row block mi of both wave rows (64 rows); `lds` holds two bands (2 x 64 x TW fp32).
 // Wide kernels: MI 4, NWN 4, NTH 512 (256 x 128*NI tiles); twin kernel: 2, 2, 2, 256 (128 x 128).
-// issued (stamped diagnostics builds only): s_memrealtime once the last store is issued
 // rpl (BCE): LDS for the per-chunk row partials, (64 MI) x (TW / 8) floats past the two band
 // buffers; nullptr: a 16-lane xor-shuffle tree per pass instead (its four dependent lane
 // exchanges behind each pass's transcendentals measured ~9 us per 256x256 tile,
@@ -384,8 +372,7 @@ __device__ __forceinline__ void st8_planes(unsigned short* cp, long long pc, int
 // wr is tile rows 128 (mi >> 1) + 64 wr + 32 (mi & 1)
 template <int EPI, int MI, int TW, int NTH, class WB, int RMAP = 0>
 __device__ __forceinline__ void epilogue_rm_w(const Params& p, const Tile& t, WB&& write_band,
-                                              float* lds, int diag, unsigned long long* issued,
-                                              float* rpl, bool vec) {
+                                              float* lds, float* rpl, bool vec) {
   constexpr int BAND = 64 * TW;  // floats per band buffer
   static_assert(TW % 128 == 0, "BCE row partials are per 128-column block");
   constexpr int CW = TW / 8;                    // 8-column chunks per band row
@@ -475,7 +462,7 @@ __device__ __forceinline__ void epilogue_rm_w(const Params& p, const Tile& t, WB
     } else {
       load_band(mi, false, sf, sb);
     }
-    if (!(diag & 4)) write_band(band, mi);
+    write_band(band, mi);
     __syncthreads();
 #pragma unroll
     for (int q = 0; q < NQ; ++q) {
@@ -515,50 +502,44 @@ __device__ __forceinline__ void epilogue_rm_w(const Params& p, const Tile& t, WB
         }
         float yv[8];
         if constexpr (BCE) {
-          if (diag & 8) {  // timing diagnostics: no transcendental math
 #pragma unroll
-            for (int j = 0; j < 8; ++j) { yv[j] = v[j]; rs += v[j] * sv[j]; v[j] = (yv[j] - sv[j]) * e.scale; }
-          } else {
+          for (int j = 0; j < 8; ++j) yv[j] = sigmoid_fast(v[j]);
+          // binary targets (every target of the wave's passes 0 or 1, a wave-uniform branch):
+          // the term is log(x ? y : 1 - y) -- the same value as the two-log form below, whose
+          // other term is exactly 0 -- at one logarithm per pixel instead of two
+          // (hardware log2 scaled by ln 2: v_log_f32 + one multiply, where __logf expands to
+          // ~12 instructions of denormal scaling and extended-precision correction)
+          bool bin = allbin;
+          if (!bin) {
+            bool b = true;
 #pragma unroll
-            for (int j = 0; j < 8; ++j) yv[j] = sigmoid_fast(v[j]);
-            // binary targets (every target of the wave's passes 0 or 1, a wave-uniform branch):
-            // the term is log(x ? y : 1 - y) -- the same value as the two-log form below, whose
-            // other term is exactly 0 -- at one logarithm per pixel instead of two
-            // (hardware log2 scaled by ln 2: v_log_f32 + one multiply, where __logf expands to
-            // ~12 instructions of denormal scaling and extended-precision correction)
-            bool bin = allbin;
-            if (!bin) {
-              bool b = true;
+            for (int j = 0; j < 8; ++j) b &= (sv[j] == 0.f) | (sv[j] == 1.f);
+            bin = __all(b);
+          }
+          if (bin) {
+            float bt[8];
 #pragma unroll
-              for (int j = 0; j < 8; ++j) b &= (sv[j] == 0.f) | (sv[j] == 1.f);
-              bin = __all(b);
-            }
-            if (bin) {
-              float bt[8];
+            for (int j = 0; j < 8; ++j)
+              bt[j] = __builtin_amdgcn_logf(sv[j] != 0.f ? yv[j] : 1.f - yv[j]) * 0.693147180559945309f;
+            if (nv == 8) {  // (the same sum in the same order, without the column mask)
 #pragma unroll
-              for (int j = 0; j < 8; ++j)
-                bt[j] = __builtin_amdgcn_logf(sv[j] != 0.f ? yv[j] : 1.f - yv[j]) * 0.693147180559945309f;
-              if (nv == 8) {  // (the same sum in the same order, without the column mask)
-#pragma unroll
-                for (int j = 0; j < 8; ++j) rs += bt[j];
-              } else {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) rs += j < nv ? bt[j] : 0.f;
-              }
+              for (int j = 0; j < 8; ++j) rs += bt[j];
             } else {
 #pragma unroll
-              for (int j = 0; j < 8; ++j) {
-                // -log(y^x (1-y)^(1-x)) with TF pow(0,0) = 1 (no epsilon), 11a/vae.py:266-269
-                const float bt = bce_term(yv[j], sv[j]);
-                rs += j < nv ? bt : 0.f;
-              }
+              for (int j = 0; j < 8; ++j) rs += j < nv ? bt[j] : 0.f;
             }
+          } else {
 #pragma unroll
-            for (int j = 0; j < 8; ++j) v[j] = (yv[j] - sv[j]) * e.scale;
+            for (int j = 0; j < 8; ++j) {
+              // -log(y^x (1-y)^(1-x)) with TF pow(0,0) = 1 (no epsilon), 11a/vae.py:266-269
+              const float bt = bce_term(yv[j], sv[j]);
+              rs += j < nv ? bt : 0.f;
+            }
           }
+#pragma unroll
+          for (int j = 0; j < 8; ++j) v[j] = (yv[j] - sv[j]) * e.scale;
         }
-        if constexpr (EPI == EPI_ACT)
-          if (!(diag & 8)) act_n(v, e.act);
+        if constexpr (EPI == EPI_ACT) act_n(v, e.act);
         if constexpr (EPI == EPI_SIGMOID) {
 #pragma unroll
           for (int j = 0; j < 8; ++j) v[j] = sigmoid_f(v[j]);
@@ -574,8 +555,7 @@ __device__ __forceinline__ void epilogue_rm_w(const Params& p, const Tile& t, WB
               if (j >= nv) yv[j] = 0.f;
         }
         const size_t o = (size_t)row * p.ldc + col0;
-        if (diag & 2) {
-        } else if (full) {
+        if (full) {
           if (e.c32) st8f(C + o, v);
           if (cp) st8_planes(cp, e.pc, e.ncp, o, v);
           if constexpr (BCE)
@@ -632,11 +612,6 @@ __device__ __forceinline__ void epilogue_rm_w(const Params& p, const Tile& t, WB
       }
     }
   }
-  if (issued) {
-    unsigned long long tt;
-    asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tt) :: "memory");
-    *issued = tt;
-  }
 }
 
 // Row-major epilogue of the 32x32-MFMA kernels (waves 2 (M) x NWN (N), acc[MI][NI] of 32x32 blocks
@@ -644,9 +619,8 @@ __device__ __forceinline__ void epilogue_rm_w(const Params& p, const Tile& t, WB
 // are always acc[0] (rotated down after each band: the band loop is not unrolled).
 template <int EPI, int MI, int NI, int NWN, int NTH>
 __device__ __forceinline__ void epilogue_rm(const Params& p, const Tile& t, f32x16 (&acc)[MI][NI],
-                                            float* lds, int wm, int wn, int diag = 0,
-                                            unsigned long long* issued = nullptr,
-                                            float* rpl = nullptr, bool vec = true) {
+                                            float* lds, int wm, int wn, float* rpl = nullptr,
+                                            bool vec = true) {
   constexpr int TW = NWN * NI * 32;
   const int lane = threadIdx.x & 63;
   auto wb = [&](float* band, int) {
@@ -662,7 +636,7 @@ __device__ __forceinline__ void epilogue_rm(const Params& p, const Tile& t, f32x
 #pragma unroll
       for (int ni = 0; ni < NI; ++ni) acc[j][ni] = acc[j + 1][ni];
   };
-  epilogue_rm_w<EPI, MI, TW, NTH>(p, t, wb, lds, diag, issued, rpl, vec);
+  epilogue_rm_w<EPI, MI, TW, NTH>(p, t, wb, lds, rpl, vec);
 }
 
 // the 128x128-tile kernels: 4 waves in 2x2, each 2x2 accumulators

@@ -122,7 +122,6 @@ __global__ __launch_bounds__(NT, 2) void gemm_f32_kernel(Params p) {
   const int lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
 
-  if (epi_skip<EPI>(p.epi)) return;
   const Tile t = tile_of(p, VAR != 2);
   const int bi = t.bi, m0 = t.m0, n0 = t.n0, ks = t.ks, ke = t.ke;
 

@@ -102,83 +102,6 @@ int bench_epilogue(Arena& ar, GemmDesc& d, int epi, int np, size_t nc) {
   return MVAE_OK;
 }
 
-// one more launch of d with a zeroed stamp buffer of `words` words, copied to h
-int stamped_launch(const GemmDesc& d, float* ws, size_t ws_n, hipStream_t st, size_t words,
-                   std::vector<unsigned long long>* h) {
-  const char* who = "";
-  Arena ar(st);
-  auto* sb = ar.alloc<unsigned long long>(words, true);
-  DIAG(ar.err);
-  GemmDesc ds = d;
-  ds.stamps = sb;
-  DIAG(gemm_run(ds, ws, ws_n, st));
-  DIAG(hipStreamSynchronize(st));
-  h->resize(words);
-  DIAG(hipMemcpy(h->data(), sb, words * 8, hipMemcpyDeviceToHost));
-  return MVAE_OK;
-}
-
-// MVAE_STAMPS=1: the stamped ring-kernel build's per-workgroup segment times (us, 100 MHz stamps)
-void print_ring_stamps(const std::vector<unsigned long long>& h, int nmax, int M, int N, int K) {
-  int n = 0, niss = 0;
-  unsigned long long lo = ~0ull, hi = 0;
-  double seg[3] = {0, 0, 0}, iss = 0, wsum = 0, vsum = 0;
-  std::vector<unsigned long long> st0s, ends;  // every workgroup's first and last stamp
-  for (int i = 0; i < nmax; ++i) {
-    const unsigned long long* q = &h[8 * (size_t)i];
-    if (!q[0]) continue;
-    ++n;
-    lo = std::min(lo, q[0]); hi = std::max(hi, q[3]);
-    st0s.push_back(q[0]); ends.push_back(q[3]);
-    for (int k = 0; k < 3; ++k) seg[k] += (double)(q[k + 1] - q[k]) * 0.01;
-    if (q[4]) { iss += (double)(q[4] - q[2]) * 0.01; ++niss; }
-    wsum += (double)q[5] * 0.01;
-    vsum += (double)q[6] * 0.01;
-  }
-  if (niss) std::fprintf(stderr, "[stamps] epilogue stores issued after %.2f us (mean of %d WGs)\n", iss / niss, niss);
-  if (!n) return;
-  std::fprintf(stderr, "[stamps] k-loop iteration boundaries (wave 0): vmcnt wait %.2f us, barrier %.2f us per WG\n", vsum / n, wsum / n);
-  std::sort(st0s.begin(), st0s.end());
-  std::sort(ends.begin(), ends.end());
-  auto us = [&](unsigned long long t) { return (t - lo) * 0.01; };
-  std::fprintf(stderr, "[stamps] M %d N %d K %d: %d workgroups, span %.2f us; mean per WG: prologue %.2f, "
-               "k-loop %.2f, epilogue %.2f us; start p50/p90/max %.2f/%.2f/%.2f; end p10/p50/max %.2f/%.2f/%.2f\n",
-               M, N, K, n, (hi - lo) * 0.01, seg[0] / n, seg[1] / n, seg[2] / n,
-               us(st0s[n / 2]), us(st0s[n * 9 / 10]), us(st0s[n - 1]), us(ends[n / 10]), us(ends[n / 2]), us(ends[n - 1]));
-}
-
-// MVAE_STAMPS=2: the stamped eight-phase build (EPI_STORE, C/D epilogue): per wave the shader
-// cycles of each of a k-tile's 8 barrier-delimited slots, summed over its k-loop; printed per
-// k-tile for waves 0-3 and 4-7 (the half one barrier behind), with the in-kernel clock (shader
-// cycles / 100 MHz realtime)
-void print_e8_stamps(const std::vector<unsigned long long>& h, size_t nwaves, int M, int N, int K) {
-  double slot[2][8] = {}, tot[2] = {}, tiles[2] = {}, cyc = 0, rt = 0, pro = 0, loop_us = 0, epi = 0;
-  int nw = 0;
-  for (size_t w = 0; w < nwaves; ++w) {
-    const unsigned long long* q = &h[16 * w];
-    if (!q[10]) continue;
-    const int half = (int)(w % 8) / 4;
-    for (int k = 0; k < 8; ++k) slot[half][k] += (double)q[k];
-    tot[half] += (double)q[8];
-    tiles[half] += (double)q[10];
-    cyc += (double)q[8];
-    rt += (double)q[9];
-    pro += (double)q[11] * 0.01;
-    loop_us += (double)q[9] * 0.01;
-    epi += (double)q[12] * 0.01;
-    ++nw;
-  }
-  if (!nw) return;
-  std::fprintf(stderr, "[e8stamps] M %d N %d K %d: %d waves, clock %.3f GHz, k-loop cycles per k-tile: "
-               "waves0-3 %.0f, waves4-7 %.0f; per workgroup: prologue %.2f us, k-loop %.2f us, epilogue %.2f us\n",
-               M, N, K, nw, cyc / rt * 0.1, tot[0] / tiles[0], tot[1] / tiles[1], pro / nw, loop_us / nw, epi / nw);
-  for (int hf = 0; hf < 2; ++hf) {
-    std::fprintf(stderr, "[e8stamps]   waves%s slots per k-tile:", hf ? "4-7" : "0-3");
-    for (int k = 0; k < 8; ++k) std::fprintf(stderr, " %.0f", slot[hf][k] / tiles[hf]);
-    std::fprintf(stderr, "\n");
-  }
-}
-
 }  // namespace
 
 extern "C" int mvae_debug_gemm(int M, int N, int K, const float* A, int lda, int at, const float* Bm,
@@ -339,10 +262,13 @@ extern "C" int mvae_bench_deint(int B, int D, int variant, int iters, void* stre
 
 // Time one GEMM shape of the step's kernel family (diagnostics): operands are allocated
 // and filled with uniform [-1,1) values inside, `iters` launches are timed with HIP events
-// on `stream` after 3 warm-ups. variant & 15: a kernel number (force_from_abi).
+// on `stream` after 3 warm-ups. variant & 15: a kernel number (force_from_abi); include/mvae.h
+// has the other bits.
 extern "C" int mvae_bench_gemm(int M, int N, int K, int at, int bt, int batch, int variant, int iters,
                                void* stream, float* avg_ms) {
   if (M <= 0 || N <= 0 || K <= 0 || iters <= 0 || !avg_ms || batch <= 0) return MVAE_EINVAL;
+  if ((variant >> 12) & 255)  // the removed kernel timing diagnostics
+    return fail(nullptr, MVAE_EINVAL, "mvae_bench_gemm: variant bits 12-19 are not supported");
   const char* who = "";
   hipStream_t st = (hipStream_t)stream;
   Arena ar(st);
@@ -359,7 +285,6 @@ extern "C" int mvae_bench_gemm(int M, int N, int K, int at, int bt, int batch, i
   d.batch = batch; d.sA = (long long)sa; d.sB = (long long)sb; d.sC = (long long)M * ldc;
   d.prec = (variant >> 4) & 15;  // 0 fp32, 1 bf16, 2 fp32-accurate bf16 split
   if (!force_desc(variant & 15, &d)) return fail(nullptr, MVAE_EINVAL, "mvae_bench_gemm: no such kernel number");
-  d.diag = (variant >> 12) & 255; // kernel timing diagnostics (results meaningless; 32: A/B switch)
   // MVAE_BENCH_SPLIT (diagnostics): split-K forced (0 / unset: the planner's)
   if (const char* sp = std::getenv("MVAE_BENCH_SPLIT"); sp && std::atoi(sp) > 0) d.force.split = std::atoi(sp);
   // MVAE_BENCH_TILE_GROUP (diagnostics): the bf16 DMA kernels' tile order (m-tiles per band)
@@ -409,19 +334,6 @@ extern "C" int mvae_bench_gemm(int M, int N, int K, int at, int bt, int batch, i
   float ms = 0.f;
   DIAG(hipEventElapsedTime(&ms, t0, t1));
   *avg_ms = ms / iters;
-  // MVAE_STAMPS=1 / 2 (diagnostics): one more launch of the stamped ring-kernel / eight-phase
-  // build, summarised on stderr
-  const char* sp = std::getenv("MVAE_STAMPS");
-  std::vector<unsigned long long> h;
-  if (sp && *sp == '1') {
-    const int nmax = 1 << 20;
-    if (int rc = stamped_launch(d, ws, ws_n, st, (size_t)8 * nmax, &h)) return rc;
-    print_ring_stamps(h, nmax, M, N, K);
-  } else if (sp && *sp == '2') {
-    const size_t nmax = 1 << 16;
-    if (int rc = stamped_launch(d, ws, ws_n, st, nmax * 8 * 16, &h)) return rc;
-    print_e8_stamps(h, nmax * 8, M, N, K);
-  }
   return MVAE_OK;
 }
 

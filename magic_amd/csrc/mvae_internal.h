@@ -17,7 +17,7 @@ enum EpiMode {
   EPI_BCEB = 5,     // EPI_BCE whose target form the epilogue chooses at run time (kernel-
                     // internal: gemm_run makes one EPI_BCEB launch when the target has a bf16
                     // plane): its bits while *xnb == 0 (GemmEpi::xbits), its bf16 plane while
-                    // *xdyn == 0, else the fp32 rows (bce_x16 / epi_skip in gemm_common.h)
+                    // *xdyn == 0, else the fp32 rows (bce_x16 in gemm_common.h)
   EPI_DACTB = 6,    // EPI_DACT reading aux from its bf16 plane auxp (kernel-internal: the wide
                     // bf16 kernels' instantiation when auxp is set, so the fp32-aux path and its
                     // registers are not compiled into it)
@@ -85,10 +85,6 @@ struct GemmDesc {
   const int* dynA = nullptr;           // != 0 when A's residual planes may be nonzero
   int prec = GEMM_F32;                 // GemmPrec
   GemmForce force;                     // what the caller fixes of the kernel choice (gemm_plan.h); default: nothing
-  int diag = 0;                        // kernel timing diagnostics (gemm_bf16.hip PParams::diag)
-  // diagnostics build of the twin kernel (mvae_bench_gemm, MVAE_STAMPS=1): per workgroup
-  // s_memrealtime stamps {start, prologue copy landed, k-loop done, end} (never in the step)
-  unsigned long long* stamps = nullptr;
   int group = -1;                      // bf16 DMA kernels' tile order (Params::group); -1 planner
   // A as bits (bf16 / f32x modes, a 0/1 operand: the layer-0 pixels): the BitMat below, read by
   // the eight-phase kernel instead of A's planes while *anb == 0 (the de-interleave's not-binary

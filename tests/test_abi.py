@@ -81,6 +81,18 @@ def test_create_rejects_removed_options(option):
     assert b"unknown option" in err and option.encode() in err, err
 
 
+@pytest.mark.parametrize("bit", [1, 2, 4, 8, 16, 32, 64, 128])
+def test_bench_gemm_refuses_removed_diagnostics(bit):
+    """mvae_bench_gemm's variant bits 12-19 selected kernel timing diagnostics that are gone: each is
+    MVAE_EINVAL with the entry's name in the message, at argument validation (before any allocation
+    or HIP call, so no GPU is needed)."""
+    lib = _lib.load()
+    ms = ctypes.c_float()
+    rc = lib.mvae_bench_gemm(256, 256, 64, 0, 0, 1, 16 | (bit << 12), 1, None, ctypes.byref(ms))
+    assert rc == -1  # MVAE_EINVAL
+    assert b"mvae_bench_gemm" in lib.mvae_last_error(None)
+
+
 def test_engine_fails_loudly_without_gpu():
     import torch
     if torch.cuda.is_available():

@@ -2,7 +2,7 @@
 # Build an A/B variant of libmvae.so: one kernel source recompiled -- with extra -D flags, or
 # replaced by another file (e.g. the previous revision from git) -- and linked with the other
 # objects of the in-tree build (magic_amd/_build). Use it with MVAE_LIB=<out>.
-#   tools/build_alt.sh magic_amd/libmvae_alt.so gemm_bf16.hip -DMVAE_QGAP=1
+#   tools/build_alt.sh magic_amd/libmvae_alt.so gemm_bf16.hip -DMY_EXPERIMENT=1   # (a macro the edited source tests)
 #   git show HEAD~3:magic_amd/csrc/gemm_bf16e.hip > /tmp/old_e8.hip
 #   tools/build_alt.sh magic_amd/libmvae_old.so gemm_bf16e.hip=/tmp/old_e8.hip
 set -e

@@ -55,7 +55,6 @@ def main():
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--config", default="C2")
     ap.add_argument("--epilogues", action="store_true", help="run each shape with its step epilogue")
-    ap.add_argument("--diag", default="0", help="kernel diagnostics bits (PParams::diag), comma list")
     ap.add_argument("--shapes", default="", help="comma list of shape names (default: all)")
     ap.add_argument("--extra", action="append", default=[],
                     help="extra shape NAME:M:N:K:AT:BT:BATCH (repeatable)")
@@ -73,7 +72,7 @@ def main():
         elif v.endswith("B"):
             v, f = v[:-1], 3 << 20
         return int(v) | f
-    variants = [(vparse(v), int(d)) for v in args.variants.split(",") for d in args.diag.split(",")]
+    variants = [vparse(v) for v in args.variants.split(",")]
     want = set(args.shapes.split(",")) if args.shapes else None
     extra = []
     for e in args.extra:
@@ -85,12 +84,12 @@ def main():
         for name, M, N, K, at, bt, batch, epi in sh:
             for v in variants:
                 ms = C.c_float()
-                vv = v[0] | (epi << 8 if args.epilogues else 0) | (v[1] << 12)
+                vv = v | (epi << 8 if args.epilogues else 0)
                 rc = lib.mvae_bench_gemm(M, N, K, at, bt, batch, vv, args.iters, st, C.byref(ms))
                 if rc != 0:
                     raise RuntimeError(lib.mvae_last_error(None))
                 res.setdefault((name, v), []).append(ms.value)
-    lab = [f"v{v & 0xfffff}" + {0: "", 1: "b", 3: "B"}[v >> 20] + (f"d{d}" if d else "") for v, d in variants]
+    lab = [f"v{v & 0xfffff}" + {0: "", 1: "b", 3: "B"}[v >> 20] for v in variants]
     print(f"{'shape':16s} {'MxNxK':>22s} batch " + " ".join(f"{x + ' TF/s':>12s}" for x in lab))
     for name, M, N, K, at, bt, batch, epi in sh:
         fl = 2.0 * M * N * K * batch

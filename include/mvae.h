@@ -126,7 +126,6 @@ int mvae_create(const mvae_cfg* cfg, int device, mvae_ctx** out);
  * the measured best plans): "name=value[,name=value...]" with e8 (256-row bf16 GEMMs: 1 planner,
  * 0 ring kernels only, 2 the eight-phase kernel wherever a 256-row kernel runs), thin_ring (0-2),
  * valu (0/1), dact_planes (0/1), bce_split (0/1), plan_log (0/1: GEMM plans on stderr),
- * conv2_half (0/1), conv2_nw (4/8/16), conv2_tpb (1/2), conv2_fpw (2/4), conv2_wg (4/8),
  * conv2_nchunk (> 0), enc_chain (0/1: bf16 mode, the encoder's hidden layers in one launch,
  * default 1), enc_chain_rows (its rows per workgroup, 16..96; 0 auto; both chains), dec_chain
  * (0/1: bf16 mode, the decoder's two hidden layers in one launch, default 1), bits (0/1: bf16 and
@@ -142,7 +141,8 @@ int mvae_create(const mvae_cfg* cfg, int device, mvae_ctx** out);
  * x3 (0-2: f32x ring-kernel plans on the plane-stacked kernels, every operand plane of a k-tile in
  * LDS at once -- 1 the tile-N-128 plans, 2 also the 256x256 ones; the same products summed in
  * another order; default 2). Every option computes valid results.
- * An unknown name or a value out of range is MVAE_EINVAL. The library reads no environment
+ * An unknown name or a value out of range is MVAE_EINVAL; so are the names of removed kernel forms
+ * (conv2_half, conv2_nw, conv2_tpb, conv2_fpw, conv2_wg: DESIGN.md 5w). The library reads no environment
  * variables (the diagnostics entry point mvae_bench_gemm aside). */
 int mvae_create_ex(const mvae_cfg* cfg, int device, const char* options, mvae_ctx** out);
 int mvae_destroy(mvae_ctx* ctx);
@@ -537,8 +537,8 @@ int mvae_bench_deint(int B, int D, int variant, int iters, void* stream, float* 
  * images, y = W2 block [1601][64]; mode 1: data gradient of x (4B images), y = W2; mode 2:
  * out[2][1601][64] = the cost / metric weight gradients of x = conv2 input (3B), y = d pre-
  * activation (4B). mfma bit 0: bf16 MFMA kernels (operands rounded to bf16), else fp32 VALU.
- * Bits 1-6: the kernel forms of the create options (bit 1 conv2_half=0, 2 conv2_nw=4, 3
- * conv2_nw=16, 4 conv2_tpb=2, 5 conv2_fpw=4, 6 conv2_wg=4). Bits 8-19: the weight gradient's
+ * Bits 1-6 are refused: MVAE_EINVAL with a message, before anything is allocated (they selected
+ * kernel forms that were removed). Bits 8-19: the weight gradient's
  * chunk count (mode 2): 0 the step's defaults min(2B, 32) VALU / min(2B, 64) MFMA, else
  * min(2B, value) for both; the slab is sized from it and prefilled with NaN bits.          */
 int mvae_debug_conv2(int S1, int B, int mode, int mfma, const float* x, const float* y, float* out,

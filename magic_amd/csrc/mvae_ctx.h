@@ -203,7 +203,7 @@ struct CreateOpts {
   int xbw_split = 2;    // the weight gradient's BitMat transposed from the forward's (mvae_ctx):
                         // 0 off, 1 on, 2 where the layer-0 forward's workgroups leave >= 32 CUs
                         // (C3 -0.6 %, C5 -0.4 %; C2, 480 forward workgroups: +3.8 % on, r6zf)
-  int conv2_nw = 8, conv2_tpb = 1, conv2_fpw = 2, conv2_wg = 8, conv2_half = 1, conv2_nchunk = 0;
+  int conv2_nchunk = 0;
 };
 
 namespace mvae {

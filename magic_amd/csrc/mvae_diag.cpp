@@ -346,22 +346,15 @@ extern "C" int mvae_debug_conv2(int S1, int B, int mode, int mfma, const float* 
                                 float* out, void* stream) {
   if (S1 <= 0 || S1 > 50 || B <= 0 || mode < 0 || mode > 2 || !x || !y || !out)
     return fail(nullptr, MVAE_EINVAL, "mvae_debug_conv2: bad argument");
+  if (mfma & 0x7e)
+    return fail(nullptr, MVAE_EINVAL, "mvae_debug_conv2: mfma bits 1-6 (the removed kernel forms) must be 0");
   const char* who = "";
   hipStream_t st = (hipStream_t)stream;
   Arena ar(st);
   ConvTower T;
   T.S1 = S1; T.S = 2 * S1; T.S2 = S1 / 2;
-  // mfma bit 0: the MFMA kernels; the kernel form (the create options' conv2_*): bit 1 the
-  // full-channel forward / data-gradient kernel, bits 2 / 3 its 4 / 16 waves, bit 4 two taps per
-  // slot, bit 5 four M-fragments per wave, bit 6 the 4-wave weight-gradient kernel; bits 8-19 the
-  // weight gradient's chunk count
+  // mfma bit 0: the MFMA kernels; bits 8-19 the weight gradient's chunk count
   T.mfma = (mfma & 1) != 0;
-  if (mfma & 2) T.conv2_half = false;
-  if (mfma & 4) T.conv2_nw = 4;
-  if (mfma & 8) T.conv2_nw = 16;
-  if (mfma & 16) T.conv2_tpb = 2;
-  if (mfma & 32) T.conv2_fpw = 4;
-  if (mfma & 64) T.conv2_wg8 = false;
   const size_t img = (size_t)S1 * S1 * 64;
   const int B2 = 2 * B;
   T.nchunk2 = std::min(B2, 32);

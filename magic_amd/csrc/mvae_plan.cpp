@@ -64,11 +64,6 @@ int mvae::parse_opts(const char* s, CreateOpts* o) {
     else if (k == "cs_one" && in(0, 2)) o->cs_one = (int)v;
     else if (k == "x3" && in(0, 2)) o->x3 = (int)v;
     else if (k == "enc_chain_rows" && (v == 0 || (in(16, 96) && v % 16 == 0))) o->enc_chain_rows = (int)v;
-    else if (k == "conv2_nw" && (v == 4 || v == 8 || v == 16)) o->conv2_nw = (int)v;
-    else if (k == "conv2_tpb" && in(1, 2)) o->conv2_tpb = (int)v;
-    else if (k == "conv2_fpw" && (v == 2 || v == 4)) o->conv2_fpw = (int)v;
-    else if (k == "conv2_wg" && (v == 4 || v == 8)) o->conv2_wg = (int)v;
-    else if (k == "conv2_half" && in(0, 1)) o->conv2_half = (int)v;
     else if (k == "conv2_nchunk" && in(0, 1 << 20)) o->conv2_nchunk = (int)v;
     else return fail(nullptr, MVAE_EINVAL, "unknown option or value out of range: " + kv);
   }
@@ -206,10 +201,6 @@ int alloc_tower(mvae_ctx* c, const CreateOpts& opt) {
   const size_t B = c->B;
   const size_t a1 = (size_t)T.S1 * T.S1 * 64, a2n = (size_t)T.S2 * T.S2 * 64;
   T.mfma = c->cfg.precision == MVAE_PREC_BF16;
-  // kernel-shape options (A/B): conv2_half=0 (full-channel forward / data gradient kernel,
-  // shaped by conv2_nw=4|16, conv2_tpb=2, conv2_fpw=4), conv2_wg=4
-  T.conv2_nw = opt.conv2_nw; T.conv2_tpb = opt.conv2_tpb; T.conv2_fpw = opt.conv2_fpw;
-  T.conv2_wg8 = opt.conv2_wg == 8; T.conv2_half = opt.conv2_half != 0;
   PLAN_ALLOC(c->xf, 3 * B * c->ldf);
   PLAN_ALLOC(c->dxf, 4 * B * c->ldf);
   PLAN_ALLOC(T.p1, 3 * B * a1);

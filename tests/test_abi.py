@@ -57,7 +57,8 @@ def test_create_rejects_bad_config_without_gpu_work():
 
 
 REMOVED_OPTIONS = ["deint_fuse=1", "deint_fuse_diag=1", "deint_variant=8", "e8_prio=1", "diag_skip_deint=1",
-                   "diag_shadow_deint=1", "diag_shadow_at=1", "diag_chain=1"]
+                   "diag_shadow_deint=1", "diag_shadow_at=1", "diag_chain=1",
+                   "conv2_half=0", "conv2_nw=4", "conv2_tpb=2", "conv2_fpw=4", "conv2_wg=4"]
 
 
 @pytest.mark.parametrize("option", REMOVED_OPTIONS)
@@ -91,6 +92,21 @@ def test_bench_gemm_refuses_removed_diagnostics(bit):
     rc = lib.mvae_bench_gemm(256, 256, 64, 0, 0, 1, 16 | (bit << 12), 1, None, ctypes.byref(ms))
     assert rc == -1  # MVAE_EINVAL
     assert b"mvae_bench_gemm" in lib.mvae_last_error(None)
+
+
+@pytest.mark.parametrize("bit", [1, 2, 3, 4, 5, 6])
+def test_debug_conv2_refuses_removed_kernel_forms(bit):
+    """mvae_debug_conv2's mfma bits 1-6 selected the conv2 kernel forms that are gone (the full-channel
+    forward / data-gradient kernel and its shapes, the 4-wave weight gradient): each is MVAE_EINVAL
+    with the entry's name in the message, at argument validation -- the pointers here are fakes that
+    nothing may read, so no GPU is needed."""
+    lib = _lib.load()
+    buf = ctypes.create_string_buffer(64)
+    p = ctypes.addressof(buf)
+    for mode in (0, 1, 2):
+        rc = lib.mvae_debug_conv2(6, 1, mode, 1 | (1 << bit), p, p, p, None)
+        assert rc == -1  # MVAE_EINVAL
+        assert b"mvae_debug_conv2" in lib.mvae_last_error(None)
 
 
 def test_engine_fails_loudly_without_gpu():

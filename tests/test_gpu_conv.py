@@ -144,7 +144,7 @@ def _conv2_ref(mode, x, y, S1, B):
     return out, mag
 
 
-def _conv2_case(mode, mfma, S1, B, form=0, chunks=0, repeat=1):
+def _conv2_case(mode, mfma, S1, B, chunks=0, repeat=1):
     """One mvae_debug_conv2 case against _conv2_ref: returns max|error| / max sum|terms|. With
     repeat > 1 the later launches must equal the first bitwise."""
     from magic_amd import _lib
@@ -163,7 +163,7 @@ def _conv2_case(mode, mfma, S1, B, form=0, chunks=0, repeat=1):
     outs = []
     for _ in range(repeat):
         out = torch.zeros(nout, device="cuda")
-        rc = lib.mvae_debug_conv2(S1, B, mode, mfma | form | (chunks << 8), xd.data_ptr(), yd.data_ptr(),
+        rc = lib.mvae_debug_conv2(S1, B, mode, mfma | (chunks << 8), xd.data_ptr(), yd.data_ptr(),
                                   out.data_ptr(), torch.cuda.current_stream().cuda_stream)
         assert rc == 0, lib.mvae_last_error(None)
         outs.append(out.cpu().numpy())
@@ -175,23 +175,16 @@ def _conv2_case(mode, mfma, S1, B, form=0, chunks=0, repeat=1):
     ref, mag = _conv2_ref(mode, xr, yr, S1, B)
     got = outs[0].astype(np.float64).reshape(ref.shape)
     err = np.abs(got - ref).max() / max(np.abs(mag).max(), 1e-30)
-    print(f"conv2 mode={mode} mfma={mfma} S1={S1} B={B} form={form} chunks={chunks}: err/mag={err:.3e}")
+    print(f"conv2 mode={mode} mfma={mfma} S1={S1} B={B} chunks={chunks}: err/mag={err:.3e}")
     return err
 
 
 @pytest.mark.parametrize("mfma", [0, 1], ids=["valu_f32", "mfma_bf16"])
 @pytest.mark.parametrize("mode", [0, 1, 2], ids=["fwd", "dgrad", "wgrad"])
 @pytest.mark.parametrize("S1,B", [(6, 2), (10, 3), (50, 1)])
-def test_conv2_kernel(mode, mfma, S1, B, form=0):
-    err = _conv2_case(mode, mfma, S1, B, form)
+def test_conv2_kernel(mode, mfma, S1, B):
+    err = _conv2_case(mode, mfma, S1, B)
     assert err <= 2e-6, err
-
-
-@pytest.mark.parametrize("mode", [0, 1], ids=["fwd", "dgrad"])
-def test_conv2_kernel_full_channel_form(mode):
-    """The full-channel forward / data-gradient kernel (mvae_debug_conv2 form bit 1, the create
-    option conv2_half=0; the default is the channel-half form) to the same bound."""
-    test_conv2_kernel(mode, 1, 50, 1, form=2)
 
 
 @pytest.mark.parametrize("mfma", [0, 1], ids=["valu_f32", "mfma_bf16"])
@@ -238,30 +231,6 @@ def test_conv2_wgrad_default_chunks_ipc2(mfma, S1, B):
     assert err <= 2e-6, err
 
 
-# form bits of mvae_debug_conv2 (bit 1: the full-channel kernel the other forward forms shape)
-FORMS = {"nw4": 2 | 4, "nw16": 2 | 8, "tpb2": 2 | 16, "nw4_fpw4": 2 | 4 | 32}
-
-
-@pytest.mark.parametrize("mode", [0, 1], ids=["fwd", "dgrad"])
-@pytest.mark.parametrize("form,S1", [("nw4", 50), ("nw4", 24), ("nw16", 50), ("nw16", 24), ("tpb2", 50),
-                                     ("tpb2", 40), ("nw4_fpw4", 50), ("nw4_fpw4", 40)])
-def test_conv2_kernel_forms(mode, form, S1):
-    """The full-channel kernel's other forms (create options conv2_nw=4|16, conv2_tpb=2,
-    conv2_fpw=4), at the benched size and a ragged one. Bands conv2_mfma_band = min(S1, slots // S1)
-    with slots = 32 nw fpw: nw4 256 slots (S1 = 50: 10 x 5; 24: 10 + 10 + 4), nw16 / tpb2 / nw4_fpw4
-    512 slots (50: 5 x 10; 24: 21 + 3; 40: 3 x 12 + 4)."""
-    err = _conv2_case(mode, 1, S1, 1, form=FORMS[form])
-    assert err <= 2e-6, err
-
-
-@pytest.mark.parametrize("S1,B,chunks", [(50, 1, 0), (24, 1, 0), (50, 2, 3)])
-def test_conv2_wgrad_four_wave_form(S1, B, chunks):
-    """conv2_wgrad_mfma_kernel (create option conv2_wg=4, form bit 6): the benched size, a ragged
-    one (R 10 + 10 + 4) and its image x row-block walk with ipc 2 and an empty chunk."""
-    err = _conv2_case(2, 1, S1, B, form=64, chunks=chunks, repeat=2)
-    assert err <= 2e-6, err
-
-
 # ------------------------------------------------------------------ whole steps at the new shapes
 @pytest.mark.parametrize("S", [4, 8, 36])
 def test_conv_step_f32_small_and_ragged(S):
@@ -275,11 +244,10 @@ def test_conv_step_f32_two_images_per_chunk():
     check_step(tiny_conv("tanh", "sqdiff", True, 10.0, image_size=12, batch=17), density=0.3)
 
 
-@pytest.mark.parametrize("options", ["conv2_nchunk=2", "conv2_half=0"])
+@pytest.mark.parametrize("options", ["conv2_nchunk=2"])
 def test_conv_step_bf16_options(options):
     """bf16 at S1 = 18 (ragged weight-gradient row blocks) with three images per chunk (create option
-    conv2_nchunk=2), and with the full-channel forward / data-gradient kernel (conv2_half=0): the
-    tolerances of test_conv_step_bf16_mfma."""
+    conv2_nchunk=2): the tolerances of test_conv_step_bf16_mfma."""
     cfg = tiny_conv("tanh", "sqdiff", True, 10.0, image_size=36, batch=3, precision="bf16", options=options)
     check_step(cfg, density=0.3, tol=5e-2, loss_tol=2e-3, dist_tol=2e-2, adam=False,
                g2_tol={"enc_conv2_W": 0.15, "enc_conv2_b": 0.15})
